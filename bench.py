@@ -14,8 +14,10 @@ carried through every kernel; results per cloud are bit-identical to one cloud a
 batch overlap the chip-wide kernels of the other.  Every step of a pass is a DIFFERENT cloud (seeds rank * D .. rank * D
 + D - 1, D = min(K, 64): BASELINE configs[2] names seeds 0..63).
 
-Timed region: PASSES (5) passes of exactly K steps, each bracketed by barrier + synchronize on both sides; `value` is the
-MEDIAN pass (min / max / all passes are in `passes`).  Prints ONE JSON line (rank 0) with, beside the contract's fields:
+Timed region: ONE pass of exactly K = --steps steps, bracketed by barrier + synchronize on both sides; `value` and `ms_per_step`
+(its duration / K) come from that pass.  --dump-outputs DIR: after the timed region, the skeleton the timed path returned for its
+last step is written to DIR as .npy files (`dump_outputs`); the inputs are the same seeded clouds on every run with the same
+arguments.  Prints ONE JSON line (rank 0) with, beside the contract's fields:
   roofline                  the kernel class with the largest summed launch duration in the timed region (HIP events on the
                             launch stream), priced against the HBM peak
   roofline_gather_scatter   the sparse-convolution family (gather / rule-GEMM / scatter) of the same timed region
@@ -72,7 +74,8 @@ STREAMS = 2     # batches in flight      } phases in turns: voxelise .. network 
 FREE_STREAMS = 3  #                       } free-running: 3 x 64 = 1.25-1.27, 3 x 48 = 1.30, 2 x 64 = 1.29, 4 x 32 = 1.29, 4 x 48 = 1.32
 MAX_DISTINCT = int(os.environ.get("ST_BENCH_DISTINCT", "64"))  # distinct clouds per rank (BASELINE configs[2]: seeds 0..63); fewer steps -> one
 #                                                              cloud per step.  ST_BENCH_DISTINCT=4: round 3's four cycled clouds (comparison aid)
-PASSES = 5         # timed passes of K steps; the median is reported
+PASSES = 1         # timed passes of K steps: one, so that --steps is the number of timed steps
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: cap on the arrays written
 UPLOAD_PASSES = 3
 SINGLE_CALLS = 7   # process_cloud calls of the single-cloud block
 REP_SET = 20       # clouds of the ground-truth-medial launch set (representative_inputs)
@@ -240,6 +243,24 @@ def parity_in_run(pipe, cloud, cpu_lc):
             "class_mismatch_fraction": cls_diff}
 
 
+def dump_outputs(sk, out_dir) -> dict:
+    """--dump-outputs: one step's skeleton as its caller receives it, in the packed layout of sharding.pack_skeleton --
+    skeleton_branches float64 [B, 5] = (tree, branch, parent, offset, length) per branch, offset / length into the point rows of
+    skeleton_xyz float32 [P, 3] and skeleton_radius float32 [P].  Returns {name: shape}."""
+    from smart_tree_amd.sharding import pack_skeleton
+
+    table, geom = pack_skeleton(sk)
+    arrays = {"skeleton_branches": table[:, 1:].numpy().astype(np.float64),  # int64 ids and counts, exact in float64
+              "skeleton_xyz": geom[:, :3].numpy().astype(np.float32),
+              "skeleton_radius": geom[:, 3].numpy().astype(np.float32)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES, "--dump-outputs: the skeleton exceeds the dump's size cap"
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def _gen_cloud(args):
     """Pool worker: one synthetic cloud into the shared host buffer (no GPU is touched in the children)."""
     n_points, seed, j = args
@@ -294,6 +315,7 @@ class CloudWorker:
             self.host.append((xyz, zeros))
             self.clouds.append(Cloud(xyz=xyz.to(device), rgb=zeros.to(device)))
         self.last = None
+        self.last_step = None  # result of the last step (last cloud of the last batch) of the latest run(): the same cloud whichever thread ends last
         self.first = 0  # offset into the resident clouds (strong_scaling_projection times other eighths of the 64)
 
     def batch_clouds(self, first, size):
@@ -422,6 +444,8 @@ class CloudWorker:
                                 self.pipes[w].skeletonizer.on_wide_phase_done = None
                                 self.pipes[w].model_inference.on_network_done = None
                         self.last = parts[-1]
+                        if i == len(batches) - 1:
+                            self.last_step = parts[-1]
                         if collect:
                             for k, sk in enumerate(parts):
                                 finished.append(pack_skeleton(sk, cloud_id=self.rank * 1_000_000 + starts[i] + k))
@@ -837,6 +861,8 @@ def main():
                          "a FIXED batch of --clouds independent clouds (seeds 0 .. clouds-1) is split round-robin over the ranks, `value` = "
                          "clouds x points / the slowest rank's time, the skeletons gathered to rank 0 inside the timed region")
     ap.add_argument("--clouds", type=int, default=0, help="--scaling strong: clouds of the whole job (default: --steps; configs[2]: 64)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write the skeleton of the timed path's last step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1008,6 +1034,10 @@ def main():
     finally:
         gc.enable()
     profiling.enable(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = {"dir": args.dump_outputs, "step": K - 1, "seed": int(seeds[(K - 1) % len(seeds)]),
+                  "arrays": dump_outputs(worker.last_step, args.dump_outputs)}
     roof = profiling.roofline(HBM_PEAK_GBS, clouds_per_launch=max(plan_batches(K, S, B)))
     stage_ms = profiling.stage_ms(K * PASSES)
     sk = worker.last
@@ -1129,6 +1159,7 @@ def main():
             "free_running": free,
             "stage_ms": stage_ms,
             "last_result": last,
+            "dump_outputs": dumped,
         }
         if world == 1 and not args.no_cpu_baseline:
             entry, cpu_lc = cpu_baseline(args.points)

@@ -24,6 +24,28 @@ def test_plan_covers_every_step_once(bench, steps, streams):
         assert plan == [steps]  # a short run is ONE launch set
 
 
+def test_dump_outputs_writes_the_packed_skeleton(bench, tmp_path):
+    """--dump-outputs: the step's skeleton in sharding.pack_skeleton's layout, float64 branch table and float32 geometry."""
+    import numpy as np
+    import torch
+
+    from smart_tree_amd.data_types.branch import BranchSkeleton
+    from smart_tree_amd.data_types.tree import DisjointTreeSkeleton, TreeSkeleton
+
+    g = torch.Generator().manual_seed(0)
+    xyz = [torch.rand((n, 3), generator=g) for n in (4, 3, 5)]
+    rad = [torch.rand((n, 1), generator=g) for n in (4, 3, 5)]
+    sk = DisjointTreeSkeleton([TreeSkeleton(0, {0: BranchSkeleton(0, -1, xyz[0], rad[0]), 1: BranchSkeleton(1, 0, xyz[1], rad[1])}),
+                               TreeSkeleton(1, {0: BranchSkeleton(0, -1, xyz[2], rad[2])})])
+    shapes = bench.dump_outputs(sk, tmp_path / "out")
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").glob("*.npy")}
+    assert shapes == {k: list(v.shape) for k, v in got.items()}
+    assert got["skeleton_branches"].dtype == np.float64 and got["skeleton_xyz"].dtype == np.float32
+    np.testing.assert_array_equal(got["skeleton_branches"], [[0, 0, -1, 0, 4], [0, 1, 0, 4, 3], [1, 0, -1, 7, 5]])
+    np.testing.assert_array_equal(got["skeleton_xyz"], torch.cat(xyz).numpy())
+    np.testing.assert_array_equal(got["skeleton_radius"], torch.cat(rad).reshape(-1).numpy())
+
+
 @pytest.mark.parametrize("world", [1, 2, 4, 8])
 def test_strong_scaling_split_of_configs2(world):
     """--scaling strong --clouds 64: the fixed batch of 64 seeds is dealt round-robin; every seed runs on exactly one rank and the

@@ -11,6 +11,9 @@ CPU restatement of the reference network as the shipped checkpoints define it
   SparseFC heads            smart_tree/model/model_blocks.py:246-285   (what the checkpoints hold)
   ModelInference tail       smart_tree/model/model_inference.py:87-88  (exp(radius)*direction, argmax)
 
+The wiring above is pinned by tests/golden/unet_wiring.npz, a float64 run of the reference's own modules over spconv
+stand-ins that use this file's rulebooks and sparse_conv (tools/make_goldens.py, tests/test_unet_wiring.py).
+
 Third-party arithmetic restated here (spconv-cu117, unpinned, source not under /root/reference
 -- parity UNPINNED; the restatement is cross-checked against dense torch conv3d /
 conv_transpose3d in tests/test_oracle_unet.py):

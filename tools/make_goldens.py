@@ -8,12 +8,15 @@ the CPU:
     outlier_removal, nn_graph / make_edges, remap_edges               (graph construction)
     sample_tree / trace_route / select_path_points, BranchSkeleton    (branch extraction)
     TreeSkeleton.prune / repair / smooth, DisjointTreeSkeleton        (post-processing)
+    Smart_Tree, SubMConvBlock, UBlock, ResBlock, SparseFC forward     (network wiring)
 The third-party calls they make are served by stand-ins that follow the canonical semantics the
-oracle documents (FRNN: brute force, d2 < r^2, ties by index; cugraph SSSP: oracle/skeleton_oracle).
+oracle documents (FRNN: brute force, d2 < r^2, ties by index; cugraph SSSP: oracle/skeleton_oracle;
+spconv convolutions: oracle/unet_oracle's rulebooks and sparse_conv in float64).
 The outputs are committed as small data fixtures; no reference source is copied and nothing from
 /root/reference is needed at test time.
 
-    python tools/make_goldens.py
+    python tools/make_goldens.py                      (every fixture)
+    python tools/make_goldens.py --only unet_wiring   (one fixture)
 """
 from __future__ import annotations
 
@@ -117,6 +120,105 @@ def install_stubs():
 
     sys.modules["spconv.pytorch.utils"].PointToVoxel = PointToVoxel
     install_graph_standins()
+    install_spconv_standins()
+
+
+# --------------------------------------------------------------------------- spconv stand-ins ---
+SPCONV_NOTE = ("spconv stand-ins (tools/make_goldens.py) restate the oracle's conventions (oracle/unet_oracle.py): kernel-offset "
+               "orientation and axis order, the strided output set and its first-appearance order, the inverse conv's reuse of the "
+               "strided pairs, and the spatial extent max+1 over the whole batch (the reference hands spconv max, sparse.py:15-18: "
+               "a documented deviation).  All arithmetic is oracle.unet_oracle.sparse_conv in float64.  The fixture pins the "
+               "reference's WIRING of those convolutions (blocks, skip, concat order, BatchNorm / ReLU placement, identity convs, "
+               "heads, normalize), not spconv's arithmetic.")
+
+
+class SparseConvTensor:
+    """spconv.SparseConvTensor: features, indices (b, z, y, x int32), spatial_shape, batch_size and the indice_dict that a strided
+    conv fills and the inverse conv with the same indice_key reads."""
+
+    def __init__(self, features, indices, spatial_shape, batch_size, indice_dict=None):
+        self.features, self.indices, self.spatial_shape, self.batch_size = features, indices, spatial_shape, batch_size
+        self.indice_dict = {} if indice_dict is None else indice_dict
+
+    def replace_feature(self, features):
+        return SparseConvTensor(features, self.indices, self.spatial_shape, self.batch_size, self.indice_dict)
+
+
+class _SparseConv(torch.nn.Module):
+    """Common part of the three conv stand-ins: spconv's argument list and its weight layout [Cout, k, k, k, Cin]."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
+                 indice_key=None, algo=None, **kw):
+        super().__init__()
+        assert not bias and dilation == 1 and groups == 1, "the network is built without bias, dilation or groups"
+        self.k, self.stride, self.padding, self.indice_key = int(kernel_size), int(stride), int(padding), indice_key
+        self.weight = torch.nn.Parameter(torch.zeros(out_channels, self.k, self.k, self.k, in_channels))
+
+    def conv(self, x, nbr, n_out):
+        from oracle import unet_oracle as uo
+
+        assert x.features.dtype == torch.float64 and self.weight.dtype == torch.float64
+        return uo.sparse_conv(x.features, nbr, self.weight.detach(), n_out)
+
+
+class SubMConv3d(_SparseConv):
+    """k 3: output set = input set, table oracle.subm_rulebook.  k 1: pointwise whatever `padding` says (submanifold)."""
+
+    def forward(self, x):
+        from oracle import unet_oracle as uo
+
+        coords = x.indices.numpy()
+        assert self.stride == 1 and self.k in (1, 3)
+        nbr = uo.subm_rulebook(coords) if self.k == 3 else np.arange(len(coords), dtype=np.int64)[None]
+        return x.replace_feature(self.conv(x, nbr, len(coords)))
+
+
+class SparseConv3d(_SparseConv):
+    """k 3 s 2 p 1: output set oracle.strided_out_coords (first-appearance order), table oracle.down_rulebook; stores
+    (fine, coarse) coordinates under its indice_key."""
+
+    def forward(self, x):
+        from oracle import unet_oracle as uo
+
+        assert (self.k, self.stride, self.padding) == (3, 2, 1) and self.indice_key is not None
+        fine = x.indices.numpy()
+        coarse = uo.strided_out_coords(fine)
+        feats = self.conv(x, uo.down_rulebook(coarse, fine), len(coarse))
+        assert self.indice_key not in x.indice_dict
+        x.indice_dict[self.indice_key] = (fine, coarse)
+        shape = [int(v) for v in (np.asarray(uo._extent(fine)) - 1) // 2 + 1]
+        return SparseConvTensor(feats, torch.from_numpy(coarse), shape, x.batch_size, x.indice_dict)
+
+
+class SparseInverseConv3d(_SparseConv):
+    """Looks its indice_key up, table oracle.up_rulebook; the output rows are the stored fine tensor's rows in that tensor's order
+    (spconv's behaviour: UBlock.forward concatenates them with the skip copy row by row)."""
+
+    def forward(self, x):
+        from oracle import unet_oracle as uo
+
+        fine, coarse = x.indice_dict[self.indice_key]
+        assert self.k == 3 and np.array_equal(x.indices.numpy(), coarse), "input is not the coarse set of its indice_key"
+        feats = self.conv(x, uo.up_rulebook(fine, coarse), len(fine))
+        return SparseConvTensor(feats, torch.from_numpy(fine), list(uo._extent(fine)), x.batch_size, x.indice_dict)
+
+
+class SparseSequential(torch.nn.Sequential):
+    """spconv.SparseSequential: sparse modules receive the tensor, every other module (BatchNorm1d, ReLU, Identity) its features."""
+
+    def add(self, module, name=None):
+        self.add_module(str(len(self._modules)) if name is None else name, module)
+
+    def forward(self, x):
+        for m in self:
+            x = m(x) if isinstance(m, (_SparseConv, SparseSequential)) else x.replace_feature(m(x.features))
+        return x
+
+
+def install_spconv_standins():
+    sp = sys.modules["spconv.pytorch"]
+    sp.SparseConvTensor, sp.SparseSequential = SparseConvTensor, SparseSequential
+    sp.SubMConv3d, sp.SparseConv3d, sp.SparseInverseConv3d = SubMConv3d, SparseConv3d, SparseInverseConv3d
 
 
 # ------------------------------------------------------------ cugraph / cudf / cupy stand-ins ---
@@ -572,6 +674,116 @@ def tree_dataset_case():
     print("tree_dataset", inputs.shape, targets.shape, coords.shape)
 
 
+VOXEL = 0.09  # ~0.4 k voxels: the fixture holds every block output of five networks in float64 (under 1 MB)
+
+
+def wiring_input():
+    """Two blocks of a voxelised procedural tree, plus isolated voxels with odd coordinates (each reaches all 8 of its coarse
+    outputs; six do not overflow the strided builders' first capacity guess n + 1024, whose retry tests/test_unet.py
+    covers) and a voxel on each coordinate-0 face of block 0."""
+    from oracle import voxel_oracle as vo
+    from smart_tree_amd.synthetic import sample_tree_cloud
+
+    c = sample_tree_cloud(9000, seed=3, scale=0.5, max_depth=4)
+    vx = vo.voxelize_cloud(vo.centre_cloud(c["xyz"]), c["rgb"], VOXEL, block_size=2.0, buffer_size=0.2)
+    keep = vx["coords"][:, 0] < 2
+    coords, xyz = vx["coords"][keep], vx["feats"][keep, :3]
+    hi = coords[:, 1:].max(0)
+    have = {tuple(r) for r in coords.tolist()}
+    extra = []
+    for b in (0, 1):  # three per block, at the corners of the odd box [1, hi - (hi + 1) % 2] that have no neighbour
+        odd = [(1, int(h - (h + 1) % 2)) for h in hi]
+        corners = [(b, z, y, x) for z in odd[0] for y in odd[1] for x in odd[2]]
+        free = [c for c in corners if not any((b, c[1] + dz, c[2] + dy, c[3] + dx) in have
+                                              for dz in (-1, 0, 1) for dy in (-1, 0, 1) for dx in (-1, 0, 1))]
+        extra += free[:3]
+    assert len(extra) == 6
+    extra += [(0, 0, hi[1] // 2, hi[2] // 2), (0, hi[0] // 2, 0, hi[2] // 2), (0, hi[0] // 2, hi[1] // 2, 0)]
+    extra = np.array([e for e in extra if tuple(e) not in have], np.int32)
+    lo = xyz.min(0)
+    ex_xyz = (lo + VOXEL * extra[:, [3, 2, 1]] + 0.01).astype(np.float32)  # xyz inside its voxel (coords are z, y, x)
+    coords, xyz = np.concatenate([coords, extra]).astype(np.int32), np.concatenate([xyz, ex_xyz]).astype(np.float32)
+    assert len(np.unique(coords, axis=0)) == len(coords)
+    for axis in (1, 2, 3):
+        assert (coords[:, axis] == 0).any()
+    return xyz, coords
+
+
+def wiring_cases():
+    """The random-weight cases: their state dicts come from tests/test_unet_wiring.py (the recipe of tests/test_unet.py with fixed
+    seeds); the fixture stores their digest, not the values."""
+    sys.path.insert(0, str(ROOT / "tests"))
+    from test_unet_wiring import random_case_weights
+
+    return {"live": (random_case_weights("live"), [8, 16, 32, 64], [8, 8, 4], 2),
+            "depth2": (random_case_weights("depth2"), [8, 16, 32], [8, 8, 4], 2),
+            "other": (random_case_weights("other"), [6, 10, 18, 34], [6, 5, 3], 3)}
+
+
+def unet_wiring_case():
+    """The reference's OWN Smart_Tree (smart_tree/model/model.py) over its SubMConvBlock / UBlock / ResBlock / Encoder / Decoder
+    blocks and SparseFC heads (model_blocks.py) -- the heads the checkpoints hold in place of the constructor's MLP heads -- with
+    BatchNorm eps 1e-4, in float64, spconv served by the stand-ins above.  Every block output is captured by forward hooks on the
+    reference's modules under the names OracleNet.trace uses."""
+    install_spconv_standins()
+    r_model = reference("smart_tree.model.model")
+    r_blocks = reference("smart_tree.model.model_blocks")
+    from oracle import unet_oracle as uo
+
+    xyz, coords = wiring_input()
+    weights_dir = ROOT / "smart_tree_amd" / "model" / "weights"
+    cases = {k: (v, None) for k, v in wiring_cases().items()}
+    cases["noble"] = ((uo.load_weights(weights_dir / "noble-elevator-58.npz"), [8, 16, 32, 64], [8, 8, 4], 2), "noble-elevator-58")
+    cases["peach"] = ((uo.load_weights(weights_dir / "peach-forest-65.npz"), [8, 16, 32, 64], [8, 8, 4], 2), "peach-forest-65")
+    out = {"xyz": xyz, "coords": coords, "note": np.array(SPCONV_NOTE), "extent": np.array("max+1 over the whole batch"),
+           "cases": np.array(list(cases))}
+    for name, ((sd, planes, fc, n_classes), ckpt) in cases.items():
+        norm, act = torch.nn.BatchNorm1d, torch.nn.ReLU
+        net = r_model.Smart_Tree(3, planes, fc + [1], fc + [3], fc + [n_classes])
+        net.radius_head = r_blocks.SparseFC(fc + [1], norm, act)
+        net.direction_head = r_blocks.SparseFC(fc + [3], norm, act)
+        net.class_head = r_blocks.SparseFC(fc + [n_classes], norm, act)
+        for m in net.modules():
+            if isinstance(m, torch.nn.BatchNorm1d):
+                m.eps = 1e-4
+        net = net.double().eval()
+        ref_sd = net.state_dict()
+        net.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        trace = {}
+
+        def hook(tag):
+            return lambda mod, inp, res: trace.__setitem__(tag, res.features.detach().numpy().copy())
+
+        net.input_conv.register_forward_hook(hook("input"))
+        level, u = 0, net.UNet
+        while True:
+            u.Head.register_forward_hook(hook(f"head{level}"))
+            if len(u.n_planes) == 1:
+                break
+            for blk, tag in ((u.Encode, "enc"), (u.Decode, "dec"), (u.Tail, "tail")):
+                blk.register_forward_hook(hook(f"{tag}{level}"))
+            level, u = level + 1, u.U
+        x = SparseConvTensor(torch.from_numpy(xyz).double(), torch.from_numpy(coords), list(uo._extent(coords)), len(coords))
+        with torch.no_grad():
+            pred = net(x)
+        out[f"{name}/ref_keys"] = np.array(list(ref_sd))
+        out[f"{name}/ref_shapes"] = np.array([",".join(str(s) for s in v.shape) for v in ref_sd.values()])
+        out[f"{name}/trace_names"] = np.array(list(trace))
+        for tag, v in trace.items():
+            out[f"{name}/trace/{tag}"] = v
+        for k in ("radius", "direction", "class_l"):
+            out[f"{name}/{k}"] = pred[k].numpy()
+        if ckpt is None:
+            from test_unet_wiring import weights_digest
+
+            out[f"{name}/weights_sha256"] = np.array(weights_digest(sd))
+        else:
+            out[f"{name}/checkpoint"] = np.array(ckpt)
+        print(name, "keys", len(ref_sd), "trace", {t: v.shape for t, v in trace.items()})
+    np.savez_compressed(OUT / "unet_wiring.npz", **out)
+    print("unet_wiring voxels", len(coords), "bytes", (OUT / "unet_wiring.npz").stat().st_size)
+
+
 def y_tree(seed=0):
     """A small trunk + two limbs with exact medial vectors and a little noise."""
     rng = np.random.RandomState(seed)
@@ -594,6 +806,13 @@ def y_tree(seed=0):
 def main():
     OUT.mkdir(parents=True, exist_ok=True)
     install_stubs()
+    if "--only" in sys.argv:  # one fixture, e.g. `--only unet_wiring`, leaving the others untouched
+        name = sys.argv[sys.argv.index("--only") + 1]
+        only = {"unet_wiring": unet_wiring_case}
+        if name not in only:
+            raise SystemExit(f"--only takes one of {sorted(only)}")
+        only[name]()
+        return
     xyz, mv = y_tree(0)
     skeleton_case("skeleton_y_tree", xyz, mv)
     # second case: procedural tree with voxel-representative points, many more branches
@@ -612,6 +831,7 @@ def main():
     tube_mesh_case()
     loss_case()
     tree_dataset_case()
+    unet_wiring_case()
 
 
 if __name__ == "__main__":

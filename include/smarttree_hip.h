@@ -305,7 +305,7 @@ int st_post_process_seg(int n_trees, const int32_t* tree_off, const int32_t* par
                         int do_smooth, int kernel_size, const int32_t* first_tree /*[n_first] first tree of every cloud*/,
                         int n_first, void* stream);
 
-/* ---- evaluation-side losses, forward only ----------------------------------
+/* ---- training / evaluation losses ----------------------------------------
  * replaces: compute_loss + L1Loss + cosine_similarity_loss + focal_loss + dice_loss (smart_tree/model/loss.py:7-97) as ONE
  *           pass over the voxels.  radius [n], direction [n,3], class_l [n,C] are the network's outputs; targets [n,5] =
  *           (radius, direction xyz, class id); mask [n] uint8 or NULL; vector_class < 0 = None.
@@ -315,6 +315,25 @@ int64_t st_loss_workspace_bytes(void);
 int st_loss_forward(const float* radius, const float* direction, const float* class_l, int n_classes, const float* targets,
                     int target_cols, const uint8_t* mask, int64_t n, int vector_class, int target_radius_log,
                     double* out_host, void* ws, int64_t ws_bytes, void* stream);
+
+/* st_loss_backward: d radius [n] (d_radius may be NULL), d direction [n,3], d class_l [n,C] of the same four terms, weighted by
+ * upstream[4] (DEVICE: radius, direction, focal, dice weights -- autograd's incoming gradients, no host synchronisation).
+ * n_vector_rows / n_class_rows = out_host[4] / out_host[5] of the forward.  Unselected rows get zeros.  Enqueue only. */
+int st_loss_backward(const float* radius, const float* direction, const float* class_l, int n_classes, const float* targets,
+                     int target_cols, const uint8_t* mask, int64_t n, int vector_class, int target_radius_log,
+                     double n_vector_rows, double n_class_rows, const float* upstream, float* d_radius, float* d_direction,
+                     float* d_class_l, void* stream);
+
+/* ---- training: sparse-convolution weight gradient ---------------------------------------------------
+ * replaces: the weight-gradient half of spconv's backward (what autograd runs through SubMConv3d / SparseConv3d /
+ *           SparseInverseConv3d in smart_tree/model/train.py:24-58).  The data gradient is st_sparse_conv_fwd over the transposed
+ *           table (smart_tree_amd/model/sparse_grad.py).
+ * dw[k][ci][co] = sum over o < n_out with nbr[k][o] >= 0 of cat(x0, x1)[nbr[k][o]][ci] * dy[o][co]; dw is [K][cin][cout] (w's
+ * layout in st_sparse_conv_fwd).  nbr NULL = pointwise (K = 1); nbr_stride 0 = n_out; n_out == 0 writes zeros.
+ * Deterministic: no float atomics, partial sums per (row chunk, offset) in ws, added in chunk order.  cin + cout <= 8192. */
+int64_t st_sparse_conv_wgrad_workspace_bytes(int K, int cin, int cout, int64_t n_out);
+int st_sparse_conv_wgrad(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                         int64_t nbr_stride, const float* dy, int cout, float* dw, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

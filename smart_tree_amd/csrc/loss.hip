@@ -1,6 +1,6 @@
 // st_loss_forward: the three training / evaluation losses of one batch in ONE pass over the voxels.
 //
-// Replaces (forward only -- SURVEY.md section 8f.4; there is no backward pass in this package)
+// Replaces (st_loss_backward at the end of this file gives the gradients)
 //   compute_loss             smart_tree/model/loss.py:7-51   (loss mask, "vector" class mask, log of the target radius)
 //   L1Loss                   smart_tree/model/loss.py:54-56  (mean |radius - log target radius| over the vector rows)
 //   cosine_similarity_loss   smart_tree/model/loss.py:59-61  (mean 1 - cos over the vector rows; torch's CosineSimilarity:
@@ -142,5 +142,102 @@ extern "C" int st_loss_forward(const float* radius, const float* direction, cons
     st_stream_wait(stream);
     ST_CHECK_LAUNCH();
     ST_REQUIRE(out_host[6] == 0.0, "loss: %lld target class ids outside [0, %d)", (long long)out_host[6], n_classes);
+    return ST_OK;
+}
+
+// st_loss_backward: the gradients of the same four terms with respect to the network's outputs, one pass over the rows, no
+// reduction (every row's gradient is its own).  Unselected rows get zeros.  The derivatives are those of the reference's
+// expressions (loss.py:54-97), evaluated in float32:
+//   L1        d radius    = w_r / n_v * sign(radius - t)                       (sign(0) = 0, as torch's)
+//   cosine    d direction = -w_d / n_v * (q^ - cos p^) / |p|                   (|p| > 1e-8; below the clamp: -w_d / n_v * q^ / 1e-8)
+//   focal     d z_j       = w_f / n_c * (2 p_t (1 - p_t) log p_t - (1 - p_t)^2) (delta_jt - p_j)
+//   dice      d z_j       = -w_x * 2 / (2 n_c + 1) * p_t (delta_jt - p_j)       (sum softmax = sum one_hot = n_c; the softmax sum
+//                                                                                has zero derivative)
+// w = upstream[0..3] (device: the backward needs no host synchronisation), n_v / n_c = the forward's selected-row counts.
+__global__ void __launch_bounds__(LS_BLOCK) k_loss_backward(LsArgs A, double n_vec, double n_cls, const float* __restrict__ upstream,
+                                                            float* __restrict__ d_radius, float* __restrict__ d_direction,
+                                                            float* __restrict__ d_class_l) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    const int C = A.n_classes;
+    const float* t = A.targets + 5 * i;
+    bool sel = !A.mask || A.mask[i];
+    const float tcf = t[4];
+    const bool tc_ok = tcf > -1.0f && tcf < (float)C;
+    const long long tc = tc_ok ? (long long)tcf : -1ll;
+    // class terms (every masked row)
+    if (d_class_l) {
+        float* dz = d_class_l + (int64_t)C * i;
+        if (sel && tc_ok) {
+            const float* z = A.class_l + (int64_t)C * i;
+            float zmax = z[0];
+            for (int k = 1; k < C; k++) zmax = z[k] > zmax ? z[k] : zmax;
+            float se = 0.0f;
+            for (int k = 0; k < C; k++) se += expf(z[k] - zmax);
+            const float lse = logf(se);
+            const float logpt = (z[tc] - zmax) - lse;
+            const float pt = expf(logpt);
+            const float om = 1.0f - pt;
+            const float cf = upstream[2] / (float)n_cls * (2.0f * pt * om * logpt - om * om);
+            const float cx = -upstream[3] * 2.0f / (float)(2.0 * n_cls + 1.0) * pt;
+            for (int k = 0; k < C; k++) {
+                const float dk = (k == tc ? 1.0f : 0.0f) - expf((z[k] - zmax) - lse);
+                dz[k] = cf * dk + cx * dk;
+            }
+        } else {
+            for (int k = 0; k < C; k++) dz[k] = 0.0f;
+        }
+    }
+    // vector terms
+    const bool vsel = sel && !(A.vector_class >= 0 && tc != (long long)A.vector_class);
+    if (d_radius) {
+        float g = 0.0f;
+        if (vsel) {
+            float tr = t[0];
+            if (A.target_radius_log) tr = logf(tr);
+            const float dr = A.radius[i] - tr;
+            g = dr > 0.0f ? upstream[0] / (float)n_vec : (dr < 0.0f ? -upstream[0] / (float)n_vec : 0.0f);
+        }
+        d_radius[i] = g;
+    }
+    if (d_direction) {
+        float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+        if (vsel) {
+            const float* d = A.direction + 3 * i;
+            const float px = d[0], py = d[1], pz = d[2], qx = t[1], qy = t[2], qz = t[3];
+            const float lp = sqrtf(px * px + py * py + pz * pz);
+            const float np = fmaxf(lp, 1e-8f), nq = fmaxf(sqrtf(qx * qx + qy * qy + qz * qz), 1e-8f);
+            const float hx = qx / nq, hy = qy / nq, hz = qz / nq;
+            const float c = -upstream[1] / (float)n_vec;
+            if (lp > 1e-8f) {
+                const float ux = px / np, uy = py / np, uz = pz / np;
+                const float cs = ux * hx + uy * hy + uz * hz;
+                gx = c * ((hx - cs * ux) / np);
+                gy = c * ((hy - cs * uy) / np);
+                gz = c * ((hz - cs * uz) / np);
+            } else {
+                gx = c * (hx / np); gy = c * (hy / np); gz = c * (hz / np);
+            }
+        }
+        float* o = d_direction + 3 * i;
+        o[0] = gx; o[1] = gy; o[2] = gz;
+    }
+}
+
+extern "C" int st_loss_backward(const float* radius, const float* direction, const float* class_l, int n_classes, const float* targets,
+                                int target_cols, const uint8_t* mask, int64_t n, int vector_class, int target_radius_log,
+                                double n_vector_rows, double n_class_rows, const float* upstream, float* d_radius, float* d_direction,
+                                float* d_class_l, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    ST_REQUIRE(n >= 0, "loss backward: n < 0");
+    ST_REQUIRE(target_cols == 5, "loss backward: targets must be [n, 5] (got %d columns)", target_cols);
+    ST_REQUIRE(n_classes >= 1 && n_classes <= LS_MAX_CLASSES, "loss backward: 1 <= classes <= %d (got %d)", LS_MAX_CLASSES, n_classes);
+    ST_REQUIRE(upstream != nullptr, "loss backward: upstream is null");
+    if (n == 0) return ST_OK;
+    ST_REQUIRE(radius && direction && class_l && targets, "loss backward: null input");
+    LsArgs A{radius, direction, class_l, targets, mask, n, n_classes, vector_class, target_radius_log};
+    hipLaunchKernelGGL(k_loss_backward, dim3((unsigned)st_div_up(n, LS_BLOCK)), dim3(LS_BLOCK), 0, stream, A, n_vector_rows, n_class_rows,
+                       upstream, d_radius, d_direction, d_class_l);
+    ST_CHECK_LAUNCH();
     return ST_OK;
 }

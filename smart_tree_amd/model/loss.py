@@ -1,11 +1,13 @@
-"""Evaluation-side losses, forward only (reference smart_tree/model/loss.py:7-97).
+"""Training / evaluation losses (reference smart_tree/model/loss.py:7-97).
 
 `compute_loss` has the reference's signature.  When it is handed THIS module's loss functions -- `L1Loss`,
 `cosine_similarity_loss`, `focal_loss` / `dice_loss`, the combination the reference trains with -- the masks, the logarithm of the
 target radius and the three reductions run as ONE HIP pass over the voxels (`st_loss_forward`, csrc/loss.hip) instead of a
 dozen torch kernels and three boolean compactions; with any other callables it does what the reference does, step by step, and
 calls them.  Used on their own, the functions below reduce whatever tensors they are given through the same kernel.
-There is no backward pass in this package: the returned tensors carry no graph.
+When a prediction requires grad (and grad mode is on), the fused path runs through an autograd Function whose backward is ONE
+more HIP pass (`st_loss_backward`): the gradients of every term with respect to radius, direction and the class logits, weighted by
+autograd's incoming gradients, which it reads on the device.  Otherwise the returned tensors carry no graph, as before.
 """
 from __future__ import annotations
 
@@ -19,7 +21,14 @@ _OUT = {"radius": 0, "direction": 1, "focal": 2, "dice": 3}
 
 
 def _forward(radius, direction, class_l, targets, mask, vector_class, target_radius_log):
-    L = _lib.lib()
+    """[radius, direction, focal, dice] losses (0-dim float32).  With grad mode on and any prediction requiring grad, through
+    `_LossFn` (differentiable in the three predictions)."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (radius, direction, class_l)):
+        return list(_LossFn.apply(radius, direction, class_l, targets, mask, vector_class, target_radius_log))
+    return _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log)[0]
+
+
+def _prepare(radius, direction, class_l, targets, mask):
     dev = radius.device
     f = lambda t: t.detach().contiguous().float()
     radius, direction, class_l, targets = f(radius).view(-1), f(direction), f(class_l), f(targets)
@@ -31,12 +40,52 @@ def _forward(radius, direction, class_l, targets, mask, vector_class, target_rad
         if mask.dtype != torch.bool or mask.shape[0] != n:
             raise ValueError("loss: mask must be a boolean tensor with one entry per row")
         m = mask.to(dev).contiguous().view(torch.uint8)
+    return radius, direction, class_l, targets, m, n
+
+
+class _LossFn(torch.autograd.Function):
+    """The four fused terms; backward = st_loss_backward (one pass, no host synchronisation)."""
+
+    @staticmethod
+    def forward(ctx, radius, direction, class_l, targets, mask, vector_class, target_radius_log):
+        prepared = _prepare(radius, direction, class_l, targets, mask)
+        vals, counts = _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log, prepared)
+        r, d, c, t, m, _ = prepared
+        ctx.save_for_backward(r, d, c, t, m)
+        ctx.meta = (vector_class, target_radius_log, counts, radius.shape, radius.dtype, direction.dtype, class_l.dtype)
+        return tuple(vals)
+
+    @staticmethod
+    def backward(ctx, g_r, g_d, g_f, g_x):
+        r, d, c, t, m = ctx.saved_tensors
+        vector_class, target_radius_log, (n_vec, n_cls), r_shape, r_dt, d_dt, c_dt = ctx.meta
+        dev = r.device
+        z = torch.zeros((), dtype=torch.float32, device=dev)
+        up = torch.stack([(g if g is not None else z).reshape(()).float() for g in (g_r, g_d, g_f, g_x)]).contiguous()
+        n, C = r.shape[0], c.shape[1]
+        dr = torch.empty(n, dtype=torch.float32, device=dev)
+        dd = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        dc = torch.empty((n, C), dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        _lib.check(L.st_loss_backward(_lib.ptr(r), _lib.ptr(d), _lib.ptr(c), C, _lib.ptr(t), t.shape[1], _lib.ptr(m), n,
+                                      -1 if vector_class is None else int(vector_class), 1 if target_radius_log else 0, n_vec, n_cls,
+                                      _lib.ptr(up), _lib.ptr(dr), _lib.ptr(dd), _lib.ptr(dc), _lib.stream(dev)))
+        need = ctx.needs_input_grad
+        return (dr.view(r_shape).to(r_dt) if need[0] else None, dd.to(d_dt) if need[1] else None, dc.to(c_dt) if need[2] else None,
+                None, None, None, None)
+
+
+def _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log, prepared=None):
+    """([radius, direction, focal, dice] losses, (vector rows, class rows)) -- one st_loss_forward call."""
+    L = _lib.lib()
+    dev = radius.device
+    radius, direction, class_l, targets, m, n = prepared or _prepare(radius, direction, class_l, targets, mask)
     out = (ctypes.c_double * 8)()
     ws = _lib.workspace(L.st_loss_workspace_bytes(), dev)
     _lib.check(L.st_loss_forward(_lib.ptr(radius), _lib.ptr(direction), _lib.ptr(class_l), class_l.shape[1], _lib.ptr(targets),
                                  targets.shape[1], _lib.ptr(m), n, -1 if vector_class is None else int(vector_class),
                                  1 if target_radius_log else 0, out, _lib.ptr(ws), ws.numel(), _lib.stream(dev)))
-    return [torch.tensor(v, dtype=torch.float32, device=dev) for v in out[:4]]
+    return [torch.tensor(v, dtype=torch.float32, device=dev) for v in out[:4]], (out[4], out[5])
 
 
 def L1Loss(outputs, targets):
@@ -114,7 +163,7 @@ def evaluate_losses(batches, model, loss_fn, device=None) -> dict:
     """Forward-only evaluation of collated batches (`model.sparse.batch_collate` items: ((inputs, targets), coords, loss_mask,
     names)): every batch through the network and `loss_fn(preds, targets, mask)`; returns the mean of each loss term over the
     batches plus their sum under "total".  This is the part of the reference's validation pass (train.py:61-84) that is a
-    forward computation; the optimiser loop, the logger and the backward pass are out of scope."""
+    forward computation; the training loop is `model.train` (train_epoch / eval_epoch)."""
     from .sparse import sparse_from_batch
 
     device = torch.device(device) if device is not None else torch.device("cuda")

@@ -1,0 +1,108 @@
+"""Autograd for the sparse convolution and the row permutation (training).
+
+The reference trains through spconv's backward (smart_tree/model/train.py:24-58).  Here:
+  * data gradient (dgrad): the forward kernel (`sparse_ops.sparse_conv`) over the TRANSPOSED neighbour table with transposed weights
+    -- gather form, no atomics, deterministic (`transposed_table` says which table that is);
+  * weight gradient (wgrad): `st_sparse_conv_wgrad` (csrc/sparse_conv_grad.hip), deterministic;
+  * `move_rows`: the gather's backward is the scatter and the other way round.
+Everything is float32; BatchNorm, ReLU, the residual add, the concat and F.normalize stay torch ops around these.
+"""
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from .. import _lib
+from . import sparse_ops as ops
+
+
+def conv_wgrad(x0: torch.Tensor, x1: Optional[torch.Tensor], nbr: Optional[torch.Tensor], n_out: int, dy: torch.Tensor,
+               K: int) -> torch.Tensor:
+    """dW [K, Cin, Cout] = sum over live pairs (i = nbr[k][o], o) of cat(x0, x1)[i]^T dy[o]; nbr None = pointwise (K = 1)."""
+    L = _lib.lib()
+    x0 = x0.contiguous()
+    x1 = x1.contiguous() if x1 is not None else None
+    dy = dy.contiguous()
+    c0 = x0.shape[1]
+    cin = c0 + (x1.shape[1] if x1 is not None else 0)
+    cout = dy.shape[1]
+    nbr_ptr, nbr_stride = ops._nbr_args(nbr)
+    dw = torch.empty((K, cin, cout), dtype=torch.float32, device=x0.device)
+    ws = _lib.workspace(L.st_sparse_conv_wgrad_workspace_bytes(K, cin, cout, n_out), x0.device)
+    _lib.check(L.st_sparse_conv_wgrad(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, nbr_stride, _lib.ptr(dy), cout,
+                                      _lib.ptr(dw), _lib.ptr(ws), ws.numel(), _lib.stream(x0.device)))
+    return dw
+
+
+def transposed_table(kind: str, pyr, level: int) -> Tuple[Optional[torch.Tensor], bool]:
+    """(table, flip) that runs a convolution's data gradient as a forward convolution: dx = conv(dy, W', table), where
+    W'[k] = W[K-1-k]^T if flip else W[k]^T.
+      "subm"  (k3 submanifold, table pyr.subm[level]):  nbr[k][o] = i  <=>  nbr[26-k][i] = o: the SAME table, offsets flipped.
+      "down"  (k3 s2, table pyr.down[level]):           nbr_down[k][o] = i  <=>  nbr_up[k][i] = o: pyr.up[level].
+      "up"    (inverse k3, table pyr.up[level]):        the other way: pyr.down[level].
+      "point" (k1):                                      no table (dx = dy W^T row by row)."""
+    if kind == "subm":
+        return pyr.subm[level], True
+    if kind == "down":
+        return pyr.up[level], False
+    if kind == "up":
+        return pyr.down[level], False
+    assert kind == "point", kind
+    return None, False
+
+
+class SparseConvFn(torch.autograd.Function):
+    """y = sum_k cat(x0, x1)[nbr[k]] W[k] (w [K, Cin, Cout]), no epilogue; backward = dgrad through the forward kernel on
+    (nbr_t, flip) from `transposed_table`, and wgrad."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, w, nbr, n_out, nbr_t, flip):
+        x0 = x0.contiguous()
+        x1 = x1.contiguous() if x1 is not None else None
+        w_d = w.detach().contiguous()
+        y = ops.sparse_conv(x0, w_d, nbr, int(n_out), x1=x1)
+        ctx.save_for_backward(x0, x1, w_d)
+        ctx.nbr, ctx.nbr_t, ctx.flip, ctx.n_out = nbr, nbr_t, flip, int(n_out)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x0, x1, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        K = w.shape[0]
+        dx0 = dx1 = dw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            wt = (w.flip(0) if ctx.flip else w).transpose(1, 2).contiguous()  # [K, Cout, Cin]
+            dx = ops.sparse_conv(dy, wt, ctx.nbr_t, x0.shape[0])
+            if x1 is None:
+                dx0 = dx
+            else:
+                c0 = x0.shape[1]
+                dx0, dx1 = dx[:, :c0].contiguous(), dx[:, c0:].contiguous()
+        if ctx.needs_input_grad[2]:
+            dw = conv_wgrad(x0, x1, ctx.nbr, ctx.n_out, dy, K)
+        return dx0, dx1, dw, None, None, None, None
+
+
+def sparse_conv(x0: torch.Tensor, w: torch.Tensor, nbr: Optional[torch.Tensor], n_out: int, nbr_t: Optional[torch.Tensor],
+                flip: bool, x1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Differentiable `sparse_ops.sparse_conv` without epilogue (see SparseConvFn)."""
+    return SparseConvFn.apply(x0, x1, w, nbr, n_out, nbr_t, flip)
+
+
+class MoveRowsFn(torch.autograd.Function):
+    """`sparse_ops.move_rows`: x[order] (gather) or out[order] = x (scatter); each is the other's backward."""
+
+    @staticmethod
+    def forward(ctx, x, order, scatter):
+        ctx.order, ctx.scatter = order, bool(scatter)
+        return ops.move_rows(x, order, scatter=scatter)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ops.move_rows(g.contiguous(), ctx.order, scatter=not ctx.scatter), None, None
+
+
+def move_rows(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> torch.Tensor:
+    return MoveRowsFn.apply(x, order, scatter)

@@ -158,7 +158,7 @@ class _SparseConv(torch.nn.Module):
         from oracle import unet_oracle as uo
 
         assert x.features.dtype == torch.float64 and self.weight.dtype == torch.float64
-        return uo.sparse_conv(x.features, nbr, self.weight.detach(), n_out)
+        return uo.sparse_conv(x.features, nbr, self.weight, n_out)  # differentiable: train_step_case takes gradients through it
 
 
 class SubMConv3d(_SparseConv):
@@ -784,6 +784,80 @@ def unet_wiring_case():
     print("unet_wiring voxels", len(coords), "bytes", (OUT / "unet_wiring.npz").stat().st_size)
 
 
+def _reference_net(r_model, r_blocks, planes, fc, n_classes):
+    """The reference's Smart_Tree with the SparseFC heads the checkpoints hold and BatchNorm eps 1e-4."""
+    norm, act = torch.nn.BatchNorm1d, torch.nn.ReLU
+    net = r_model.Smart_Tree(3, planes, fc + [1], fc + [3], fc + [n_classes])
+    net.radius_head = r_blocks.SparseFC(fc + [1], norm, act)
+    net.direction_head = r_blocks.SparseFC(fc + [3], norm, act)
+    net.class_head = r_blocks.SparseFC(fc + [n_classes], norm, act)
+    for m in net.modules():
+        if isinstance(m, torch.nn.BatchNorm1d):
+            m.eps = 1e-4
+    return net
+
+
+def train_step_case():
+    """One training step of the reference's OWN Smart_Tree (SparseFC heads, BatchNorm eps 1e-4) in float64 train mode on
+    wiring_input(), spconv served by the stand-ins above: the reference's compute_loss with L1Loss / cosine_similarity_loss /
+    focal_loss, vector_class 0, target_radius_log (conf/training.yaml), then backward.  Stores the outputs, the three loss terms,
+    a digest of every parameter's gradient (tests/test_train_step.py grad_digest: sums and a strided sample in float64; the test
+    holds a float64 oracle step to it and the HIP gradients to that step entrywise) and the BatchNorm running statistics after the
+    step.  Cases: the noble-elevator-58 checkpoint,
+    training.yaml's [8, 16, 32] (random weights "depth2") and the "other" widths of wiring_cases()."""
+    install_spconv_standins()
+    r_model = reference("smart_tree.model.model")
+    r_blocks = reference("smart_tree.model.model_blocks")
+    r_loss = reference("smart_tree.model.loss")
+    from oracle import unet_oracle as uo
+
+    sys.path.insert(0, str(ROOT / "tests"))
+    from test_train_step import grad_digest
+
+    xyz, coords = wiring_input()
+    n = len(coords)
+    g = torch.Generator().manual_seed(21)
+    t_dir = torch.nn.functional.normalize(torch.randn(n, 3, generator=g, dtype=torch.float64))
+    targets = torch.cat([torch.rand(n, 1, generator=g, dtype=torch.float64) * 0.19 + 0.01, t_dir,
+                         (torch.rand(n, 1, generator=g, dtype=torch.float64) < 0.4).double()], 1)
+    mask = torch.rand(n, generator=g) < 0.85
+    wc = wiring_cases()
+    weights_dir = ROOT / "smart_tree_amd" / "model" / "weights"
+    cases = {"noble": ((uo.load_weights(weights_dir / "noble-elevator-58.npz"), [8, 16, 32, 64], [8, 8, 4], 2), "noble-elevator-58"),
+             "depth2": (wc["depth2"], None), "other": (wc["other"], None)}
+    out = {"xyz": xyz, "coords": coords, "targets": targets.numpy(), "mask": mask.numpy(), "cases": np.array(list(cases)),
+           "note": np.array(SPCONV_NOTE)}
+    for name, ((sd, planes, fc, n_classes), ckpt) in cases.items():
+        net = _reference_net(r_model, r_blocks, planes, fc, n_classes).double().train()
+        net.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}, strict=True)
+        x = SparseConvTensor(torch.from_numpy(xyz).double(), torch.from_numpy(coords), list(uo._extent(coords)), n)
+        pred = net(x)
+        loss = r_loss.compute_loss(pred, targets, mask, radius_loss_fn=r_loss.L1Loss, direction_loss_fn=r_loss.cosine_similarity_loss,
+                                   class_loss_fn=r_loss.focal_loss, target_radius_log=True, vector_class=0)
+        sum(loss.values()).backward()
+        for k in ("radius", "direction", "class_l"):
+            out[f"{name}/{k}"] = pred[k].detach().numpy().astype(np.float32)  # float32 storage: far below every test bar
+        out[f"{name}/losses"] = np.array([float(loss[k]) for k in ("radius", "direction", "class_l")], np.float64)
+        params = dict(net.named_parameters())
+        out[f"{name}/param_keys"] = np.array(list(params))
+        for k, p in params.items():
+            assert p.grad is not None, k
+            out[f"{name}/grad_digest/{k}"] = grad_digest(p.grad.numpy())  # the full tensors would not be a small fixture
+        for k, v in net.state_dict().items():
+            if k.endswith(("running_mean", "running_var")):
+                out[f"{name}/running/{k}"] = v.numpy().astype(np.float32)
+        if ckpt is None:
+            from test_unet_wiring import weights_digest
+
+            out[f"{name}/weights_sha256"] = np.array(weights_digest(sd))
+        else:
+            out[f"{name}/checkpoint"] = np.array(ckpt)
+        zero = [k for k, p in params.items() if not p.grad.abs().max() > 0]
+        print(name, "losses", out[f"{name}/losses"].tolist(), "params", len(params), "exactly-zero gradients", len(zero))
+    np.savez_compressed(OUT / "train_step.npz", **out)
+    print("train_step voxels", n, "bytes", (OUT / "train_step.npz").stat().st_size)
+
+
 def y_tree(seed=0):
     """A small trunk + two limbs with exact medial vectors and a little noise."""
     rng = np.random.RandomState(seed)
@@ -808,7 +882,7 @@ def main():
     install_stubs()
     if "--only" in sys.argv:  # one fixture, e.g. `--only unet_wiring`, leaving the others untouched
         name = sys.argv[sys.argv.index("--only") + 1]
-        only = {"unet_wiring": unet_wiring_case}
+        only = {"unet_wiring": unet_wiring_case, "train_step": train_step_case}
         if name not in only:
             raise SystemExit(f"--only takes one of {sorted(only)}")
         only[name]()
@@ -832,6 +906,7 @@ def main():
     loss_case()
     tree_dataset_case()
     unet_wiring_case()
+    train_step_case()
 
 
 if __name__ == "__main__":

@@ -335,6 +335,23 @@ int64_t st_sparse_conv_wgrad_workspace_bytes(int K, int cin, int cout, int64_t n
 int st_sparse_conv_wgrad(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
                          int64_t nbr_stride, const float* dy, int cout, float* dw, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- mixed-precision (autocast float16) training (csrc/sparse_conv_half.hip) ----------------------------
+ * replaces: spconv's half-precision conv forward and backward under torch.cuda.amp.autocast (model/train.py:24-58 with
+ *           conf/training.yaml fp16: True): SubMConv3d / SparseConv3d / SparseInverseConv3d, model/model_blocks.py:8-285.
+ * st_sparse_conv_h_fwd: y = sum_k cat(x0, x1)[nbr[k]] . W[k]; x0, x1, w [K][cin][cout] (plain layout) and y are IEEE half, the
+ * sums float32, one rounding to half at the store; no epilogue.  Any cin, cout >= 1 and concat split (as st_sparse_conv_fwd's
+ * generic kernel); nbr NULL = pointwise (K = 1); nbr_stride 0 = n_out.  The data gradient is this call over the transposed table.
+ * st_sparse_conv_wgrad_h: st_sparse_conv_wgrad with half x0 / x1 / dy; dw float32, accumulated in float32, deterministic
+ * (partial slabs per (row chunk, offset) in ws, added in chunk order).  cin + cout <= 8192.
+ * Neither clamps: inf / NaN operands reach every sum they take part in.
+ * st_move_rows_h: st_move_rows for rows of `row_elems` 2-byte elements (1..512, odd counts included). */
+int st_sparse_conv_h_fwd(const void* x0, int c0, const void* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                         int64_t nbr_stride, const void* w, int cout, void* y, void* stream);
+int64_t st_sparse_conv_wgrad_h_workspace_bytes(int K, int cin, int cout, int64_t n_out);
+int st_sparse_conv_wgrad_h(const void* x0, int c0, const void* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                           int64_t nbr_stride, const void* dy, int cout, float* dw, void* ws, int64_t ws_bytes, void* stream);
+int st_move_rows_h(const void* src, int row_elems, const int32_t* order, int64_t n, void* dst, int scatter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,10 @@ SIGNATURES = {
     "st_loss_backward": (c_int, [P, P, P, c_int, P, c_int, P, I64, c_int, c_int, c_double, c_double, P, P, P, P, P]),
     "st_sparse_conv_wgrad_workspace_bytes": (I64, [c_int, c_int, c_int, I64]),
     "st_sparse_conv_wgrad": (c_int, [P, c_int, P, c_int, P, c_int, I64, I64, P, c_int, P, P, I64, P]),
+    "st_sparse_conv_h_fwd": (c_int, [P, c_int, P, c_int, P, c_int, I64, I64, P, c_int, P, P]),
+    "st_sparse_conv_wgrad_h_workspace_bytes": (I64, [c_int, c_int, c_int, I64]),
+    "st_sparse_conv_wgrad_h": (c_int, [P, c_int, P, c_int, P, c_int, I64, I64, P, c_int, P, P, I64, P]),
+    "st_move_rows_h": (c_int, [P, c_int, P, I64, P, c_int, P]),
     "st_skeleton_components": (c_int, [c_int, P, P, I64, P, P, P, P, P, P, c_float, c_int, c_int, P, P, P, P, P, P, P, P,
                                        P, P, ctypes.POINTER(I64), P, I64, P]),
 }
@@ -119,6 +123,7 @@ ENQUEUE_ONLY = frozenset({
     "st_knn_radius_seg", "st_skeleton_workspace_bytes_seg", "st_post_process_seg", "st_radius_count_seg",
     "st_voxelize_cloud_workspace_bytes", "st_loss_workspace_bytes", "st_spatial_order_workspace_bytes", "st_spatial_order", "st_connected_components_knn", "st_component_csr_knn", "st_component_csr_knn_workspace_bytes", "st_move_rows",
     "st_loss_backward", "st_sparse_conv_wgrad_workspace_bytes", "st_sparse_conv_wgrad",
+    "st_sparse_conv_h_fwd", "st_sparse_conv_wgrad_h_workspace_bytes", "st_sparse_conv_wgrad_h", "st_move_rows_h",
 })
 
 

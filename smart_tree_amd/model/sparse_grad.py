@@ -5,7 +5,14 @@ The reference trains through spconv's backward (smart_tree/model/train.py:24-58)
     -- gather form, no atomics, deterministic (`transposed_table` says which table that is);
   * weight gradient (wgrad): `st_sparse_conv_wgrad` (csrc/sparse_conv_grad.hip), deterministic;
   * `move_rows`: the gather's backward is the scatter and the other way round.
-Everything is float32; BatchNorm, ReLU, the residual add, the concat and F.normalize stay torch ops around these.
+BatchNorm, ReLU, the residual add, the concat and F.normalize stay torch ops around these.
+
+Half path (mixed-precision training, the reference's `fp16: True`): under `torch.autocast(<device type>, dtype=torch.float16)`, or
+with float16 features, the convolution casts features and weight to half (as spconv's `custom_fwd(cast_inputs=torch.float16)`
+convs do), runs `st_sparse_conv_h_fwd` (csrc/sparse_conv_half.hip) and returns half.  Its backward: the data gradient is the same
+kernel over the transposed table with half W', the weight gradient `st_sparse_conv_wgrad_h` (float32 sums) returned as float32 for
+the float32 master weight -- never rounded to half (spconv would return a half dW that autograd then widens: an intended
+difference).  Autocast to any other dtype keeps the float32 path.
 """
 from __future__ import annotations
 
@@ -35,6 +42,34 @@ def conv_wgrad(x0: torch.Tensor, x1: Optional[torch.Tensor], nbr: Optional[torch
     return dw
 
 
+def conv_wgrad_half(x0: torch.Tensor, x1: Optional[torch.Tensor], nbr: Optional[torch.Tensor], n_out: int, dy: torch.Tensor,
+                    K: int) -> torch.Tensor:
+    """`conv_wgrad` for float16 x0 / x1 / dy (st_sparse_conv_wgrad_h): dW [K, Cin, Cout] float32, float32 sums, deterministic."""
+    L = _lib.lib()
+    x0 = x0.contiguous()
+    x1 = x1.contiguous() if x1 is not None else None
+    dy = dy.contiguous()
+    if x0.dtype != torch.float16 or dy.dtype != torch.float16 or (x1 is not None and x1.dtype != torch.float16):
+        raise ValueError("conv_wgrad_half takes float16 features and gradients")
+    c0 = x0.shape[1]
+    cin = c0 + (x1.shape[1] if x1 is not None else 0)
+    cout = dy.shape[1]
+    nbr_ptr, nbr_stride = ops._nbr_args(nbr)
+    dw = torch.empty((K, cin, cout), dtype=torch.float32, device=x0.device)
+    ws = _lib.workspace(L.st_sparse_conv_wgrad_h_workspace_bytes(K, cin, cout, n_out), x0.device)
+    _lib.check(L.st_sparse_conv_wgrad_h(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, nbr_stride, _lib.ptr(dy), cout,
+                                        _lib.ptr(dw), _lib.ptr(ws), ws.numel(), _lib.stream(x0.device)))
+    return dw
+
+
+def half_path(x0: torch.Tensor) -> bool:
+    """The convolution runs in half storage: float16 features, or float16 autocast on the features' device type."""
+    if x0.dtype == torch.float16:
+        return True
+    dt = x0.device.type
+    return torch.is_autocast_enabled(dt) and torch.get_autocast_dtype(dt) == torch.float16
+
+
 def transposed_table(kind: str, pyr, level: int) -> Tuple[Optional[torch.Tensor], bool]:
     """(table, flip) that runs a convolution's data gradient as a forward convolution: dx = conv(dy, W', table), where
     W'[k] = W[K-1-k]^T if flip else W[k]^T.
@@ -58,6 +93,16 @@ class SparseConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, x1, w, nbr, n_out, nbr_t, flip):
+        ctx.half = half_path(x0)
+        if ctx.half:
+            ctx.dtypes = (x0.dtype, x1.dtype if x1 is not None else None, w.dtype)
+            x0 = x0.detach().to(torch.float16).contiguous()
+            x1 = x1.detach().to(torch.float16).contiguous() if x1 is not None else None
+            w_h = w.detach().to(torch.float16).contiguous()
+            y = ops.sparse_conv_half(x0, w_h, nbr, int(n_out), x1=x1)
+            ctx.save_for_backward(x0, x1, w_h)
+            ctx.nbr, ctx.nbr_t, ctx.flip, ctx.n_out = nbr, nbr_t, flip, int(n_out)
+            return y
         x0 = x0.contiguous()
         x1 = x1.contiguous() if x1 is not None else None
         w_d = w.detach().contiguous()
@@ -68,6 +113,8 @@ class SparseConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        if ctx.half:
+            return SparseConvFn._backward_half(ctx, dy)
         x0, x1, w = ctx.saved_tensors
         dy = dy.contiguous()
         K = w.shape[0]
@@ -84,10 +131,31 @@ class SparseConvFn(torch.autograd.Function):
             dw = conv_wgrad(x0, x1, ctx.nbr, ctx.n_out, dy, K)
         return dx0, dx1, dw, None, None, None, None
 
+    @staticmethod
+    def _backward_half(ctx, dy):
+        x0, x1, w = ctx.saved_tensors  # float16
+        dy = dy.to(torch.float16).contiguous()
+        K = w.shape[0]
+        dx0 = dx1 = dw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            wt = (w.flip(0) if ctx.flip else w).transpose(1, 2).contiguous()  # [K, Cout, Cin] half
+            dx = ops.sparse_conv_half(dy, wt, ctx.nbr_t, x0.shape[0])
+            if x1 is None:
+                dx0 = dx
+            else:
+                c0 = x0.shape[1]
+                dx0, dx1 = dx[:, :c0].contiguous(), dx[:, c0:].contiguous()
+            dx0 = dx0.to(ctx.dtypes[0])
+            dx1 = dx1.to(ctx.dtypes[1]) if dx1 is not None else None
+        if ctx.needs_input_grad[2]:
+            dw = conv_wgrad_half(x0, x1, ctx.nbr, ctx.n_out, dy, K).to(ctx.dtypes[2])  # float32 for a float32 weight
+        return dx0, dx1, dw, None, None, None, None
+
 
 def sparse_conv(x0: torch.Tensor, w: torch.Tensor, nbr: Optional[torch.Tensor], n_out: int, nbr_t: Optional[torch.Tensor],
                 flip: bool, x1: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Differentiable `sparse_ops.sparse_conv` without epilogue (see SparseConvFn)."""
+    """Differentiable `sparse_ops.sparse_conv` without epilogue (see SparseConvFn); half storage under float16 autocast or with
+    float16 features (`half_path`)."""
     return SparseConvFn.apply(x0, x1, w, nbr, n_out, nbr_t, flip)
 
 
@@ -97,11 +165,18 @@ class MoveRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, order, scatter):
         ctx.order, ctx.scatter = order, bool(scatter)
-        return ops.move_rows(x, order, scatter=scatter)
+        return _move(x, order, scatter)
 
     @staticmethod
     def backward(ctx, g):
-        return ops.move_rows(g.contiguous(), ctx.order, scatter=not ctx.scatter), None, None
+        return _move(g.contiguous(), ctx.order, not ctx.scatter), None, None
+
+
+def _move(x, order, scatter):
+    """float16 rows (any width) through st_move_rows_h, 4-byte rows through st_move_rows."""
+    if x.dtype == torch.float16:
+        return ops.move_rows_half(x, order, scatter=scatter)
+    return ops.move_rows(x, order, scatter=scatter)
 
 
 def move_rows(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> torch.Tensor:

@@ -213,6 +213,43 @@ def move_rows(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> to
     return out
 
 
+def move_rows_half(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> torch.Tensor:
+    """`move_rows` for a float16 [N, C] tensor, any C (st_move_rows_h)."""
+    L = _lib.lib()
+    x = x.contiguous()
+    assert x.dtype == torch.float16 and x.ndim == 2 and order.dtype == torch.int32
+    out = torch.empty_like(x)
+    if x.shape[1]:
+        _lib.check(L.st_move_rows_h(_lib.ptr(x), x.shape[1], _lib.ptr(order), x.shape[0], _lib.ptr(out), int(scatter),
+                                    _lib.stream(x.device)))
+    return out
+
+
+def sparse_conv_half(x0: torch.Tensor, w: torch.Tensor, nbr: Optional[torch.Tensor], n_out: int,
+                     x1: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = sum_k cat(x0, x1)[nbr[k]] W[k] in half storage (st_sparse_conv_h_fwd): x0, x1, w [K, Cin, Cout] float16, float32 sums,
+    y float16; any widths and concat split, no epilogue (training: BatchNorm / ReLU stay torch ops)."""
+    L = _lib.lib()
+    K, cin, cout = w.shape
+    if x0.dtype != torch.float16 or w.dtype != torch.float16 or (x1 is not None and x1.dtype != torch.float16):
+        raise ValueError("sparse_conv_half takes float16 features and weights")
+    c0 = x0.shape[1]
+    if c0 + (x1.shape[1] if x1 is not None else 0) != cin:
+        raise ValueError(f"input channels {c0} + {x1.shape[1] if x1 is not None else 0} do not match the weights' {cin}")
+    nbr_ptr, nbr_stride = _nbr_args(nbr)
+    y = torch.empty((n_out, cout), dtype=torch.float16, device=x0.device)
+    if n_out == 0:
+        return y
+    nbytes = (lambda: (_pair_count(nbr) if nbr is not None else n_out) * (cin * 2 + (4 if nbr is not None else 0))
+              + n_out * cout * 2) if profiling.enabled() else 0
+    nflops = (lambda: 2.0 * (_pair_count(nbr) if nbr is not None else n_out) * cin * cout) if profiling.enabled() else 0
+    form = "k_hconv_mfma" if cin >= 16 and cout >= 16 else "k_hconv_vec"  # csrc/sparse_conv_half.hip hconv_matrix_form
+    with profiling.kernel(f"{form}<{cin},{cout}>" + ("" if nbr is not None else " k1"), nbytes, nflops):
+        _lib.check(L.st_sparse_conv_h_fwd(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, nbr_stride, _lib.ptr(w), cout,
+                                          _lib.ptr(y), _lib.stream(x0.device)))
+    return y
+
+
 def mfma_weight(w: torch.Tensor) -> torch.Tensor:
     """[K, Cin, Cout] -> the MFMA operand order wp[K][Cin/16][4][Cout][4] = W[k][16c + 4kg + s][co]."""
     K, cin, cout = w.shape

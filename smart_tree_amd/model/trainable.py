@@ -9,7 +9,11 @@ sparse convolutions are HIP kernels with a backward pass (model/sparse_grad.py).
   goes the other way.
 * BatchNorm, ReLU, the residual add, the concat and F.normalize are torch ops (train mode: batch statistics, running statistics
   updated with momentum 0.1; eval mode: running statistics).  The rulebooks and the row order are those `Smart_Tree.features`
-  picks.  float32 only.
+  picks.
+* Precision: float32, or mixed precision as the reference trains with `fp16: True` -- under `torch.autocast(<device type>,
+  dtype=torch.float16)` (`train.train_epoch(..., fp16=True, scaler=...)`) or with float16 features the convolutions run in half
+  storage with float32 sums (model/sparse_grad.py), except the direction head's output conv (see `forward`); parameters, their
+  gradients and `state_dict()` stay float32.
 """
 from __future__ import annotations
 
@@ -103,8 +107,9 @@ class _UBlock(nn.Module):
 class _SparseFC(nn.Module):
     """SparseFC (model_blocks.py:246-285): pointwise conv + BatchNorm + ReLU per hidden width, then a pointwise conv."""
 
-    def __init__(self, planes):
+    def __init__(self, planes, float_last=False):
         super().__init__()
+        self.float_last = float_last
         mods = []
         for i in range(len(planes) - 2):
             mods += [SparseConvWeight(planes[i], planes[i + 1], 1), _bn(planes[i + 1]), nn.ReLU()]
@@ -113,8 +118,13 @@ class _SparseFC(nn.Module):
 
     def forward(self, x):
         n = x.shape[0]
+        last = self.sequence[-1]
         for m in self.sequence:
-            if isinstance(m, SparseConvWeight):
+            if m is last and self.float_last and sg.half_path(x):
+                # float32 output conv in a mixed-precision step (see TrainableSmartTree.forward)
+                with torch.autocast(x.device.type, enabled=False):
+                    x = m(x.float(), None, n, None, False)
+            elif isinstance(m, SparseConvWeight):
                 x = m(x, None, n, None, False)
             elif isinstance(m, nn.ReLU):
                 x = F.relu(x)
@@ -128,13 +138,14 @@ class TrainableSmartTree(nn.Module):
                  fp16: bool = False):
         super().__init__()
         if fp16:
-            raise ValueError("TrainableSmartTree trains in float32 only (no half-precision training)")
+            raise ValueError("TrainableSmartTree keeps float32 parameters and has no fp16 argument: for mixed-precision training "
+                             "run it under torch.autocast(device_type, dtype=torch.float16), e.g. train_epoch(..., fp16=True, scaler=...)")
         if bias:
             raise ValueError("the network is built without bias (as the reference's default)")
         self.input_conv = _Block(input_channels, unet_planes[0], 1)
         self.UNet = _UBlock(unet_planes)
         self.radius_head = _SparseFC(radius_fc_planes)
-        self.direction_head = _SparseFC(direction_fc_planes)
+        self.direction_head = _SparseFC(direction_fc_planes, float_last=True)
         self.class_head = _SparseFC(class_fc_planes)
         self.depth = len(unet_planes) - 1
         self.use_bricks = True
@@ -180,8 +191,8 @@ class TrainableSmartTree(nn.Module):
 
     def features(self, sparse_input) -> torch.Tensor:
         feats = sparse_input.features.contiguous()
-        if feats.dtype != torch.float32:
-            raise ValueError("TrainableSmartTree trains in float32 only")
+        if feats.dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"TrainableSmartTree takes float32 or float16 features (got {feats.dtype})")
         pyr, order, x = self._pyramid(sparse_input, feats)
         x = self.input_conv(x, None, x.shape[0], None, False)
         x = self.UNet(x, pyr, 0)
@@ -191,4 +202,8 @@ class TrainableSmartTree(nn.Module):
 
     def forward(self, sparse_input) -> Dict[str, torch.Tensor]:
         x = self.features(sparse_input)
+        # Mixed precision: the direction head's last (pointwise, 4 -> 3) conv runs in float32, so F.normalize sees float32.  A row whose
+        # hidden ReLUs are all off has an exactly zero direction; normalize's gradient there is g / eps (eps = 1e-12), finite in
+        # float32 and masked by the ReLUs below, but inf once rounded to half -- then 0 * inf = NaN in that conv's weight gradient and
+        # GradScaler would skip every step while such rows exist (a random-init network has many).
         return {"radius": self.radius_head(x), "direction": F.normalize(self.direction_head(x)), "class_l": self.class_head(x)}

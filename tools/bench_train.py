@@ -6,7 +6,10 @@ synthetic tree, 2 cm voxels, every block in one batch), Adam.  Prints one JSON l
   forward of the same layer (st_sparse_conv_fwd, same tensors): time, the ratio wgrad / forward, and the fraction of the HBM peak at
   the forward's algorithmic bytes P * (Cin * 4 + 4) + n_out * Cout * 4 (P = live pairs; pointwise: P = n_out, no index bytes).
 
-    python tools/bench_train.py [--steps 10] [--warmup 3] [--points 1000000] [--voxel 0.02]
+    python tools/bench_train.py [--steps 10] [--warmup 3] [--points 1000000] [--voxel 0.02] [--fp16]
+
+--fp16: the AMP step (forward + loss under float16 autocast, backward of the scaled loss, GradScaler + Adam) on the same batch; the
+family is then every st_sparse_conv_wgrad_h call next to the st_sparse_conv_h_fwd of the same layer (bytes at 2 per feature element).
 """
 import argparse
 import functools
@@ -52,6 +55,7 @@ def main():
     ap.add_argument("--points", type=int, default=1_000_000)
     ap.add_argument("--voxel", type=float, default=0.02)
     ap.add_argument("--reps", type=int, default=10, help="replays per wgrad / forward layer timing")
+    ap.add_argument("--fp16", action="store_true", help="mixed precision: float16 autocast + GradScaler (half convolution kernels)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
 
@@ -76,15 +80,22 @@ def main():
 
     ev = lambda: torch.cuda.Event(enable_timing=True)
     phases = {"forward": [], "backward": [], "optimizer": []}
+    scaler = torch.amp.GradScaler("cuda") if args.fp16 else None
+    amp = lambda: torch.autocast("cuda", dtype=torch.float16, enabled=args.fp16)
     for step in range(args.warmup + args.steps):
         e0, e1, e2, e3 = ev(), ev(), ev(), ev()
         e0.record()
-        loss = loss_fn(net(sp), targets, mask)
-        total = sum(loss.values())
+        with amp():
+            loss = loss_fn(net(sp), targets, mask)
+            total = sum(loss.values())
         e1.record()
-        total.backward()
+        (scaler.scale(total) if args.fp16 else total).backward()
         e2.record()
-        opt.step()
+        if args.fp16:
+            scaler.step(opt)
+            scaler.update()
+        else:
+            opt.step()
         opt.zero_grad()
         e3.record()
         torch.cuda.synchronize()
@@ -96,31 +107,36 @@ def main():
 
     # the wgrad family: record the calls of one backward pass, replay each one on its own next to the layer's forward
     calls = []
-    real = sg.conv_wgrad
+    wname = "conv_wgrad_half" if args.fp16 else "conv_wgrad"
+    real = getattr(sg, wname)
+    fwd = ops.sparse_conv_half if args.fp16 else ops.sparse_conv
+    esz = 2 if args.fp16 else 4
 
     def recording(x0, x1, nbr, n_out, dy, K):
         calls.append((x0, x1, nbr, n_out, dy, K))
         return real(x0, x1, nbr, n_out, dy, K)
 
-    sg.conv_wgrad = recording
+    setattr(sg, wname, recording)
     try:
-        sum(loss_fn(net(sp), targets, mask).values()).backward()
+        with amp():
+            total = sum(loss_fn(net(sp), targets, mask).values())
+        total.backward()
     finally:
-        sg.conv_wgrad = real
+        setattr(sg, wname, real)
     opt.zero_grad()
     layers, tot_w, tot_f, tot_bytes = [], 0.0, 0.0, 0
     for x0, x1, nbr, n_out, dy, K in calls:
         cin = x0.shape[1] + (x1.shape[1] if x1 is not None else 0)
         cout = dy.shape[1]
-        w = torch.randn(K, cin, cout, device=dev)
+        w = torch.randn(K, cin, cout, device=dev, dtype=x0.dtype)
         t_w = _events_ms(lambda: real(x0, x1, nbr, n_out, dy, K), args.reps)
-        t_f = _events_ms(lambda: ops.sparse_conv(x0, w, nbr, n_out, x1=x1), args.reps)
+        t_f = _events_ms(lambda: fwd(x0, w, nbr, n_out, x1=x1), args.reps)
         pairs = int((nbr >= 0).sum()) if nbr is not None else n_out
-        nbytes = pairs * (cin * 4 + (4 if nbr is not None else 0)) + n_out * cout * 4
+        nbytes = pairs * (cin * esz + (4 if nbr is not None else 0)) + n_out * cout * esz
         layers.append({"K": K, "cin": cin, "cout": cout, "n_out": n_out, "pairs": pairs, "wgrad_ms": round(t_w, 4),
                        "fwd_ms": round(t_f, 4), "ratio": round(t_w / t_f, 2), "wgrad_hbm_frac": round(nbytes / (t_w * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)})
         tot_w, tot_f, tot_bytes = tot_w + t_w, tot_f + t_f, tot_bytes + nbytes
-    out = {"metric": "train_step", "voxels": n, "steps": args.steps, "warmup": args.warmup,
+    out = {"metric": "train_step_fp16" if args.fp16 else "train_step", "voxels": n, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": round(sum(ms.values()), 3), "ms": {k: round(v, 3) for k, v in ms.items()},
            "loss_last": {k: float(v.detach()) for k, v in loss.items()},
            "wgrad": {"calls": len(calls), "ms_total": round(tot_w, 3), "fwd_ms_total_same_layers": round(tot_f, 3),

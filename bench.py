@@ -1,8 +1,12 @@
 """Headline benchmark: input points/s of the smart-tree inference path on 1M-point synthetic trees.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU; clouds are sharded, weak scaling -- every rank runs K clouds of its own;
      --scaling strong --clouds 64: BASELINE.json configs[2] as written, a FIXED batch split round-robin over the ranks)
+
+A plain run does what its headline figure needs and no more: it generates its K clouds, settles, warms up, times the K steps,
+writes --dump-outputs and prints the line.  Every other measurement and check runs only with --full (after the timed region:
+they leave the headline figure as a plain run measures it); --no-cpu-baseline / --no-extras / --free-running trim or extend it.
 
 A step = one pass of the hot path (CentreCloud -> blocks/voxelise -> UNet -> class filter -> kNN graph -> components
 -> SSSP -> sample_tree -> prune/repair/smooth -> host copy of the skeleton) over ONE 1M-point synthetic tree
@@ -21,11 +25,14 @@ arguments.  Prints ONE JSON line (rank 0) with, beside the contract's fields:
   roofline                  the kernel class with the largest summed launch duration in the timed region (HIP events on the
                             launch stream), priced against the HBM peak
   roofline_gather_scatter   the sparse-convolution family (gather / rule-GEMM / scatter) of the same timed region
+  stage_ms                  per-stage ms per step of the same timed region
+and, with --full only:
   single_cloud              SURVEY 8d's literal metric: median wall time of >= 5 `Pipeline.process_cloud(cloud=...)` calls
                             with the cloud in PINNED HOST memory (the upload is inside the call), per-stage ms, and the
                             convolution family's roofline for one cloud at a time
   value_incl_host_upload    the same K steps with every cloud uploaded from pinned host memory inside the pass (copy stream,
                             the next batch's upload overlaps the current batch's kernels); median of 3 passes
+  roofline_solo             (N = 1) one batch alone on the GPU, every launch bracketed: solo kernel durations
   representative_e2e        (N = 1) the same K clouds through the whole path with the skeleton stage fed the GENERATOR's exact medial
                             vectors (the network still runs and is timed): one end-to-end figure on the regime the reference runs
                             the skeleton stage in -- the shipped checkpoint's output on the benchmark tree is arbitrary and gives a
@@ -35,9 +42,12 @@ arguments.  Prints ONE JSON line (rank 0) with, beside the contract's fields:
   cpu_baseline              (N = 1) the oracle -- a port of the reference algorithm; the reference itself is CUDA-only --
                             timed on this host's cores on one full cloud, whose skeleton is also compared with the GPU's
                             for the same cloud (`parity_in_run`).
+  helper_workgroups, representative_inputs, other_configs   (N = 1; not with --no-extras) the skeleton stage on ground-truth
+                            medial vectors and at the training scale, and BASELINE.json's other single-GPU configurations
+  free_running              (N = 1, --free-running) the same K steps with no ordering of the batches in flight
 
 Environment (all optional): ST_BENCH_ORDERED 3 (default: batches in flight take turns with voxelise .. network) / 1 (with the
-whole chip-filling phase) / 0 (free-running); ST_BENCH_MIN_UPTIME_S (30: the warm-up lasts until the process is that old);
+whole chip-filling phase) / 0 (free-running); ST_BENCH_MIN_UPTIME_S (20: the settle passes last until the process is that old);
 ST_BENCH_BLOCKING_SYNC (1: host waits block instead of spinning; default: by the number of host cores); ST_BENCH_TORCH_THREADS (1); ST_BENCH_SELECT_THREADS,
 ST_SKELETON_PARAMS (developer knobs); ST_BENCH_DRYRUN=1 (multi-rank control flow on one GPU over gloo).
 """
@@ -51,13 +61,15 @@ import threading
 import time
 from pathlib import Path
 
-# A bench that starts right after another GPU process has exited -- the round-end sequence pytest -> smoke -> bench -- runs in a
-# slow state for its first ~15-20 s on the gpurun boxes (profiles/r02_after_another_process.txt): 2.5-2.9 ms per cloud instead of
-# 1.30, every stage that ends in a count read-back 5-10x longer; an idle probe of such a read-back shows nothing (20 us).
-# HSA_ENABLE_SDMA=0 (host copies by shader kernels) shortens it, waiting it out removes it: the warm-up lasts until the process
-# is MIN_UPTIME seconds old (with either copy path 1.29-1.30 ms per cloud then; the SDMA engines stay on: faster uploads).
+# A bench that starts right after another GPU process has exited -- the sequence pytest -> smoke -> bench -- has been measured
+# in a slow state for its first ~15-20 s (profiles/r02_after_another_process.txt): 2.5-2.9 ms per cloud instead of 1.30, every
+# stage that ends in a count read-back 5-10x longer; an idle probe of such a read-back shows nothing (20 us).  HSA_ENABLE_SDMA=0
+# (host copies by shader kernels) shortens it, waiting it out removes it: the settle passes last until the process is MIN_UPTIME
+# seconds old (1.29-1.30 ms per cloud then, with either copy path; the SDMA engines stay on: faster uploads), and give up
+# SETTLE_GRACE seconds later if no two passes have agreed -- a plain run spends at most ~30 s outside its steps.
 T_PROCESS = time.perf_counter()
-MIN_UPTIME = float(os.environ.get("ST_BENCH_MIN_UPTIME_S", "30"))  # warm-up lasts at least until the process is this old
+MIN_UPTIME = float(os.environ.get("ST_BENCH_MIN_UPTIME_S", "20"))  # the settle passes last at least until the process is this old
+SETTLE_GRACE = 4.0  # ... and at most this much longer
 
 import numpy as np
 import torch
@@ -850,10 +862,14 @@ def main():
     ap.add_argument("--steps", type=int, default=384)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--points", type=int, default=N_POINTS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs[3] / configs[4] batches")
-    ap.add_argument("--free-running", action="store_true", help="one GPU: an extra untimed pass with 3 batches in flight and no "
-                    "ordering of their chip-filling phases, reported as `free_running` (profiles/r02_free_running.txt)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, every other measurement and check of the benchmark: "
+                    "single_cloud, value_incl_host_upload, roofline_solo; one GPU: representative_e2e, the strong-scaling projection, "
+                    "cpu_baseline + parity_in_run, representative_inputs, other_configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline / parity_in_run")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the ground-truth / training-scale probes, the "
+                    "strong-scaling projection and the configs[3] / configs[4] batches")
+    ap.add_argument("--free-running", action="store_true", help="with --full, one GPU: an extra untimed pass with 3 batches in flight "
+                    "and no ordering of their chip-filling phases, reported as `free_running` (profiles/r02_free_running.txt)")
     ap.add_argument("--batch", type=int, default=MAX_BATCH, help="clouds per launch set (Pipeline.process_clouds); 1 = one cloud per call")
     ap.add_argument("--streams", type=int, default=STREAMS, help="batches in flight per GPU (one host thread + HIP stream each)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
@@ -864,6 +880,8 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed region, write the skeleton of the timed path's last step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.free_running and not args.full:
+        ap.error("--free-running is a measurement of --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -881,7 +899,7 @@ def main():
     # pass is a different cloud (BASELINE configs[2]: seeds 0..63; rank r draws r * D .. r * D + D - 1, rank 0's first is seed 0)
     n_distinct = max(1, min(MAX_DISTINCT, K))
     t_gen = time.perf_counter()
-    want_rep = world == 1 and not args.no_extras
+    want_rep = world == 1 and args.full and not args.no_extras
     # one GPU: configs[2]'s 64 seeds are generated whatever --steps says (the timed region uses the first n_distinct of them; the
     # strong-scaling projection times launch sets of 8 .. 64 clouds), each with the generator's exact medial vectors (representative_e2e)
     n_gen = max(n_distinct, PROJECTION_CLOUDS) if want_rep and not strong else n_distinct
@@ -977,8 +995,9 @@ def main():
     # stream has its own allocator pool, and batches differ a little in their voxel / vertex counts -- a pool that has seen only
     # one batch still grows during the next few (hipMalloc synchronises the device: measured 2.1 instead of 1.55 ms per cloud when
     # the timed region started after one warm-up batch per stream); and a process that starts right after another GPU process has
-    # exited -- the round-end sequence pytest -> smoke -> bench -- runs with inflated host round trips for its first ~15-20 s on the
-    # gpurun boxes (profiles/r02_after_another_process.txt: passes agree with each other at 2.5-2.9 ms per cloud, then drop to 1.3).
+    # exited -- the sequence pytest -> smoke -> bench -- has run with inflated host round trips for its first ~15-20 s
+    # (profiles/r02_after_another_process.txt: passes agree with each other at 2.5-2.9 ms per cloud, then drop to 1.3).  Past
+    # MIN_UPTIME + SETTLE_GRACE the passes end whether or not two have agreed.
     settle_steps, t_settle = 0, time.perf_counter()
     warm_last_ms = None
     if plan and MIN_UPTIME >= 0:
@@ -994,7 +1013,7 @@ def main():
             cur = time.perf_counter() - t0
             settle_steps += sum(plan)
             uptime = time.perf_counter() - T_PROCESS
-            if (prev is not None and abs(cur - prev) <= 0.05 * prev and uptime >= MIN_UPTIME) or uptime > MIN_UPTIME + 45.0:
+            if (prev is not None and abs(cur - prev) <= 0.05 * prev and uptime >= MIN_UPTIME) or uptime > MIN_UPTIME + SETTLE_GRACE:
                 break
             prev = cur
         profiling.enable(False)
@@ -1006,8 +1025,6 @@ def main():
         finished.clear()
         finished.extend(worker.run(plan_batches(warm, S, B), collect=world > 1, streams=S))
     gather()
-    fence()
-    single = worker.single_cloud() if world == 1 and args.warmup > 0 else None  # (--warmup 0: the PMC passes of tools/collect_r5.sh want the batch's launches alone)
     fence()
     # kernel timers of the timed region: the convolutions of a forward pass are bracketed ONCE as a family (a pair of events
     # around each of the 26 launches cost ~10 us apiece between kernels that otherwise run back to back); the per-class table
@@ -1042,17 +1059,23 @@ def main():
     stage_ms = profiling.stage_ms(K * PASSES)
     sk = worker.last
     last = {"trees": len(sk.skeletons), "branches": int(sum(len(t.branches) for t in sk.skeletons))}
+    # --full: every other measurement, after the timed region (a plain run has what its result line needs)
+    single = None
+    if args.full and world == 1 and args.warmup > 0:  # (--warmup 0: the PMC passes of tools/collect_r5.sh want the batch's launches alone)
+        fence()
+        single = worker.single_cloud()
     # the same K clouds with the host -> device upload of every cloud inside the pass (pinned host buffers, copy streams)
     up_s = []
-    run_steps(K, upload=True)  # (untimed: the copy streams' allocator pools)
-    gather()
-    for _ in range(UPLOAD_PASSES):
-        fence()
-        t1 = time.perf_counter()
-        run_steps(K, upload=True)
+    if args.full:
+        run_steps(K, upload=True)  # (untimed: the copy streams' allocator pools)
         gather()
-        fence()
-        up_s.append(time.perf_counter() - t1)
+        for _ in range(UPLOAD_PASSES):
+            fence()
+            t1 = time.perf_counter()
+            run_steps(K, upload=True)
+            gather()
+            fence()
+            up_s.append(time.perf_counter() - t1)
     free = None
     if S_free > 1:
         plan_free = plan_batches(K, S_free, B)
@@ -1073,7 +1096,7 @@ def main():
     # for the record: ONE batch at a time on one stream with the kernel timers on -- solo kernel durations (in the timed region
     # the kernels of the batches in flight share the chip, which inflates every bracket)
     roof_solo = None
-    if world == 1:
+    if args.full and world == 1:
         profiling.family_mode(False)  # every launch bracketed: the per-class table
         profiling.enable(True)
         worker.run([min(B, max(K, 1))], collect=False, streams=1)
@@ -1097,7 +1120,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         pass_s, up_s = t[:PASSES].tolist(), t[PASSES:].tolist()
     med = lambda v: sorted(v)[len(v) // 2]
-    dt, dt_up = med(pass_s), med(up_s)
+    dt, dt_up = med(pass_s), (med(up_s) if up_s else None)
 
     if rank == 0:
         value = total_clouds * args.points / dt
@@ -1110,10 +1133,12 @@ def main():
             "dtype": "f32", "data": "synthetic",
             "passes": {"n": PASSES, "statistic": "median", "ms_per_step": [round(1e3 * v / (total_clouds if strong else K), 4) for v in pass_s],
                        "value_min": total_clouds * args.points / max(pass_s), "value_max": total_clouds * args.points / min(pass_s)},
-            "value_incl_host_upload": total_clouds * args.points / dt_up,
-            "incl_host_upload": {"passes": UPLOAD_PASSES, "statistic": "median", "ms_per_step": [round(1e3 * v / (total_clouds if strong else K), 4) for v in up_s],
-                                 "note": "every cloud of the pass is copied from pinned host memory inside the pass (24 bytes per point: xyz + rgb); "
-                                         "a worker enqueues its NEXT batch's copies on a copy stream before the current batch's kernels"},
+            "full": args.full,
+            "value_incl_host_upload": None if dt_up is None else total_clouds * args.points / dt_up,
+            "incl_host_upload": None if dt_up is None else {
+                "passes": UPLOAD_PASSES, "statistic": "median", "ms_per_step": [round(1e3 * v / (total_clouds if strong else K), 4) for v in up_s],
+                "note": "every cloud of the pass is copied from pinned host memory inside the pass (24 bytes per point: xyz + rgb); "
+                        "a worker enqueues its NEXT batch's copies on a copy stream before the current batch's kernels"},
             "config": {"workload": f"configs[1]: one {args.points}-point synthetic tree per rank per step, 2 cm voxels, "
                                    "noble-elevator-58 weights, full Pipeline path with prune/repair/smooth; steps run in "
                                    "batches of clouds through ONE launch set (Pipeline.process_clouds)",
@@ -1127,12 +1152,12 @@ def main():
                        "strong_scaling_projection": projection,
                        "clouds_per_launch_set": max(batches), "batches_in_timed_region": len(batches),
                        "batches_in_flight_per_gpu": S, "host_threads_per_gpu": S,
-                       "settle_s": round(settle_s, 1), "settle_steps": settle_steps,
+                       "setup_s": round(t_settle - T_PROCESS, 1), "settle_s": round(settle_s, 1), "settle_steps": settle_steps,
                        "settle_note": "untimed passes over the timed region's own batches before the --warmup steps, until two passes agree "
-                                      "to 5 % and the process is `warmup_until_process_age_s` old (allocator pools, clock ramp after "
+                                      f"to 5 % and the process is `warmup_until_process_age_s` old, {SETTLE_GRACE:g} s later at most (allocator pools, clock ramp after "
                                       "another GPU process)",
-                       "value_incl_host_upload": total_clouds * args.points / dt_up,
-                       "ms_per_step_incl_host_upload": 1e3 * dt_up / (total_clouds if strong else K),
+                       "value_incl_host_upload": None if dt_up is None else total_clouds * args.points / dt_up,
+                       "ms_per_step_incl_host_upload": None if dt_up is None else 1e3 * dt_up / (total_clouds if strong else K),
                        "single_cloud_ms": None if single is None else single["ms"],
                        "schedule": {1: "the chip-filling phases (voxelise .. adjacency) of the batches in flight take turns; a batch's "
                                        "skeleton stage (one compute unit per tree) overlaps with the other batch's chip-filling phase",
@@ -1161,11 +1186,11 @@ def main():
             "last_result": last,
             "dump_outputs": dumped,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             entry, cpu_lc = cpu_baseline(args.points)
             out["cpu_baseline"] = entry
             out.update(parity_in_run(worker.pipes[0], worker.clouds[0], cpu_lc))
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             from smart_tree_amd.skeleton import skeletonize
             out["helper_workgroups"] = skeletonize.helper_stats()  # lost > 0: a fall-back of the helper protocol ran (slower, not wrong)
             del worker

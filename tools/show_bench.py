@@ -5,10 +5,11 @@ import sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(f"value {d['value'] / 1e6:.1f} M points/s, {d['ms_per_step']:.3f} ms per step (steps {d['steps']}, warm-up {d['warmup']}); "
       f"passes {d['passes']['ms_per_step']}")
-print(f"incl. host upload {d['value_incl_host_upload'] / 1e6:.1f} M points/s; passes {d['incl_host_upload']['ms_per_step']}")
+if d.get("value_incl_host_upload"):  # (bench.py --full)
+    print(f"incl. host upload {d['value_incl_host_upload'] / 1e6:.1f} M points/s; passes {d['incl_host_upload']['ms_per_step']}")
 c = d["config"]
 print("config:", {k: c.get(k) for k in ("distinct_clouds_per_rank", "clouds_per_launch_set", "batches_in_timed_region", "batches_in_flight_per_gpu",
-                                        "cloud_generation_s", "warmup_steps_run", "host_cpu_cores_busy_in_timed_region")})
+                                        "cloud_generation_s", "setup_s", "settle_s", "host_cpu_cores_busy_in_timed_region")})
 r = d["roofline"] or {}
 print("roofline:", {k: r.get(k) for k in ("kernel", "bound", "frac", "achieved", "avg_us", "launches", "total_ms", "dominant_by_chip_time", "traffic",
                                           "algorithmic_bytes_per_launch")})

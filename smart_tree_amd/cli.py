@@ -1,37 +1,16 @@
 """`run-smart-tree` entry point (reference smart_tree/cli.py:10-26) without hydra: the YAML `_target_`
 tree is instantiated by a small recursive loader, `+path=...` / `+directory=...` and `a.b=value`
-overrides are accepted on the command line."""
+overrides are accepted on the command line (smart_tree_amd/config.py)."""
 from __future__ import annotations
 
-import importlib
 import sys
 from pathlib import Path
 
-import yaml
-
-
-def instantiate(node):
-    if isinstance(node, list):
-        return [instantiate(v) for v in node]
-    if not isinstance(node, dict):
-        return node
-    kwargs = {k: instantiate(v) for k, v in node.items() if k != "_target_"}
-    if "_target_" not in node:
-        return kwargs
-    module, _, name = node["_target_"].rpartition(".")
-    return getattr(importlib.import_module(module), name)(**kwargs)
+from .config import apply_overrides, instantiate, load_yaml  # noqa: F401  (instantiate: part of this module's interface)
 
 
 def load_config(overrides=()):
-    cfg = yaml.safe_load((Path(__file__).resolve().parent / "conf" / "pipeline.yaml").read_text())
-    for item in overrides:
-        key, _, value = item.lstrip("+").partition("=")
-        node = cfg
-        parts = key.split(".")
-        for p in parts[:-1]:
-            node = node.setdefault(p, {})
-        node[parts[-1]] = yaml.safe_load(value)
-    return cfg
+    return apply_overrides(load_yaml(Path(__file__).resolve().parent / "conf" / "pipeline.yaml"), overrides)
 
 
 def main(argv=None):

@@ -352,6 +352,26 @@ int st_sparse_conv_wgrad_h(const void* x0, int c0, const void* x1, int cin, cons
                            int64_t nbr_stride, const void* dy, int cout, float* dw, void* ws, int64_t ws_bytes, void* stream);
 int st_move_rows_h(const void* src, int row_elems, const int32_t* order, int64_t n, void* dst, int scatter, void* stream);
 
+/* ---- training: BatchNorm over [n, C] rows, synchronised across ranks (csrc/batchnorm.hip) ----------------
+ * replaces: torch.nn.BatchNorm1d's training forward and backward (model_blocks.py), with the batch statistics of the whole global
+ *           batch: the caller all-reduces the small float64 vectors between the passes (smart_tree_amd/model/sync_bn.py).
+ * half = 0: x / dy / y / dx float32; half = 1: IEEE half, float32 math.  mean, invstd, gamma, beta are float32 [C] device vectors.
+ * st_bn_stats:           out [2C + 1] float64 = sum x | sum x^2 | n.
+ * st_bn_apply:           y = (x - mean) * invstd * gamma + beta.
+ * st_bn_backward_stats:  out [2C] float64 = sum dy | sum dy * xhat, xhat = (x - mean) * invstd recomputed from x.
+ * st_bn_backward_apply:  dx = gamma * invstd * (dy - sum_dy / N - xhat * sum_dy_xhat / N); sums [2C] and count [1] (= N) are float64
+ *                        device values (the all-reduced backward stats and the forward's global row count).
+ * The two stats calls are deterministic: per-chunk partials in ws (st_bn_workspace_bytes), added in a fixed order, no float
+ * atomics.  n = 0 launches no kernel (the stats calls zero `out`).  1 <= C <= 4096.  Enqueue only. */
+int64_t st_bn_workspace_bytes(int64_t n, int C);
+int st_bn_stats(const void* x, int half, int64_t n, int C, double* out, void* ws, int64_t ws_bytes, void* stream);
+int st_bn_apply(const void* x, int half, int64_t n, int C, const float* mean, const float* invstd, const float* gamma,
+                const float* beta, void* y, void* stream);
+int st_bn_backward_stats(const void* x, const void* dy, int half, int64_t n, int C, const float* mean, const float* invstd,
+                         double* out, void* ws, int64_t ws_bytes, void* stream);
+int st_bn_backward_apply(const void* x, const void* dy, int half, int64_t n, int C, const float* mean, const float* invstd,
+                         const float* gamma, const double* sums, const double* count, void* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

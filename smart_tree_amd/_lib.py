@@ -102,6 +102,11 @@ SIGNATURES = {
     "st_sparse_conv_wgrad_h_workspace_bytes": (I64, [c_int, c_int, c_int, I64]),
     "st_sparse_conv_wgrad_h": (c_int, [P, c_int, P, c_int, P, c_int, I64, I64, P, c_int, P, P, I64, P]),
     "st_move_rows_h": (c_int, [P, c_int, P, I64, P, c_int, P]),
+    "st_bn_workspace_bytes": (I64, [I64, c_int]),
+    "st_bn_stats": (c_int, [P, c_int, I64, c_int, P, P, I64, P]),
+    "st_bn_apply": (c_int, [P, c_int, I64, c_int, P, P, P, P, P, P]),
+    "st_bn_backward_stats": (c_int, [P, P, c_int, I64, c_int, P, P, P, P, I64, P]),
+    "st_bn_backward_apply": (c_int, [P, P, c_int, I64, c_int, P, P, P, P, P, P, P]),
     "st_skeleton_components": (c_int, [c_int, P, P, I64, P, P, P, P, P, P, c_float, c_int, c_int, P, P, P, P, P, P, P, P,
                                        P, P, ctypes.POINTER(I64), P, I64, P]),
 }
@@ -124,6 +129,7 @@ ENQUEUE_ONLY = frozenset({
     "st_voxelize_cloud_workspace_bytes", "st_loss_workspace_bytes", "st_spatial_order_workspace_bytes", "st_spatial_order", "st_connected_components_knn", "st_component_csr_knn", "st_component_csr_knn_workspace_bytes", "st_move_rows",
     "st_loss_backward", "st_sparse_conv_wgrad_workspace_bytes", "st_sparse_conv_wgrad",
     "st_sparse_conv_h_fwd", "st_sparse_conv_wgrad_h_workspace_bytes", "st_sparse_conv_wgrad_h", "st_move_rows_h",
+    "st_bn_workspace_bytes", "st_bn_stats", "st_bn_apply", "st_bn_backward_stats", "st_bn_backward_apply",
 })
 
 

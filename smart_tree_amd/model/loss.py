@@ -20,12 +20,13 @@ from .. import _lib
 _OUT = {"radius": 0, "direction": 1, "focal": 2, "dice": 3}
 
 
-def _forward(radius, direction, class_l, targets, mask, vector_class, target_radius_log):
+def _forward(radius, direction, class_l, targets, mask, vector_class, target_radius_log, raw_out=None):
     """[radius, direction, focal, dice] losses (0-dim float32).  With grad mode on and any prediction requiring grad, through
-    `_LossFn` (differentiable in the three predictions)."""
+    `_LossFn` (differentiable in the three predictions).  `raw_out` (a list) receives the kernel's float64 [radius, direction,
+    focal, dice, vector rows, class rows]."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (radius, direction, class_l)):
-        return list(_LossFn.apply(radius, direction, class_l, targets, mask, vector_class, target_radius_log))
-    return _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log)[0]
+        return list(_LossFn.apply(radius, direction, class_l, targets, mask, vector_class, target_radius_log, raw_out))
+    return _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log, raw_out=raw_out)[0]
 
 
 def _prepare(radius, direction, class_l, targets, mask):
@@ -47,9 +48,9 @@ class _LossFn(torch.autograd.Function):
     """The four fused terms; backward = st_loss_backward (one pass, no host synchronisation)."""
 
     @staticmethod
-    def forward(ctx, radius, direction, class_l, targets, mask, vector_class, target_radius_log):
+    def forward(ctx, radius, direction, class_l, targets, mask, vector_class, target_radius_log, raw_out=None):
         prepared = _prepare(radius, direction, class_l, targets, mask)
-        vals, counts = _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log, prepared)
+        vals, counts = _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log, prepared, raw_out)
         r, d, c, t, m, _ = prepared
         ctx.save_for_backward(r, d, c, t, m)
         ctx.meta = (vector_class, target_radius_log, counts, radius.shape, radius.dtype, direction.dtype, class_l.dtype)
@@ -72,10 +73,10 @@ class _LossFn(torch.autograd.Function):
                                       _lib.ptr(up), _lib.ptr(dr), _lib.ptr(dd), _lib.ptr(dc), _lib.stream(dev)))
         need = ctx.needs_input_grad
         return (dr.view(r_shape).to(r_dt) if need[0] else None, dd.to(d_dt) if need[1] else None, dc.to(c_dt) if need[2] else None,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
-def _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log, prepared=None):
+def _forward_values(radius, direction, class_l, targets, mask, vector_class, target_radius_log, prepared=None, raw_out=None):
     """([radius, direction, focal, dice] losses, (vector rows, class rows)) -- one st_loss_forward call."""
     L = _lib.lib()
     dev = radius.device
@@ -85,6 +86,8 @@ def _forward_values(radius, direction, class_l, targets, mask, vector_class, tar
     _lib.check(L.st_loss_forward(_lib.ptr(radius), _lib.ptr(direction), _lib.ptr(class_l), class_l.shape[1], _lib.ptr(targets),
                                  targets.shape[1], _lib.ptr(m), n, -1 if vector_class is None else int(vector_class),
                                  1 if target_radius_log else 0, out, _lib.ptr(ws), ws.numel(), _lib.stream(dev)))
+    if raw_out is not None:
+        raw_out.append(list(out[:6]))
     return [torch.tensor(v, dtype=torch.float32, device=dev) for v in out[:4]], (out[4], out[5])
 
 
@@ -136,12 +139,14 @@ _FUSED_CLASS = {focal_loss: _OUT["focal"], dice_loss: _OUT["dice"]}
 
 
 def compute_loss(preds, targets, mask=None, radius_loss_fn=None, direction_loss_fn=None, class_loss_fn=None,
-                 target_radius_log=True, vector_class=None):
+                 target_radius_log=True, vector_class=None, raw_out=None):
     """loss.py:7-51.  preds: {"radius" [n,1], "direction" [n,3], "class_l" [n,C]}; targets [n,5] = radius, direction, class.
     The fused dice term one-hot encodes over the C classes of the logits; the reference's `F.one_hot(targets)` infers the width
-    from the largest id PRESENT and raises a shape mismatch for a batch that lacks class C-1 -- here such a batch is evaluated."""
+    from the largest id PRESENT and raises a shape mismatch for a batch that lacks class C-1 -- here such a batch is evaluated.
+    raw_out (fused path only, a list): receives the kernel's float64 [radius, direction, focal, dice, vector rows, class rows]
+    (data-parallel training weights each rank's terms with them, model/data_parallel.py)."""
     if radius_loss_fn is L1Loss and direction_loss_fn is cosine_similarity_loss and class_loss_fn in _FUSED_CLASS:
-        out = _forward(preds["radius"], preds["direction"], preds["class_l"], targets, mask, vector_class, target_radius_log)
+        out = _forward(preds["radius"], preds["direction"], preds["class_l"], targets, mask, vector_class, target_radius_log, raw_out)
         return {"radius": out[0], "direction": out[1], "class_l": out[_FUSED_CLASS[class_loss_fn]]}
     # foreign loss functions: the reference's own sequence of selections
     radius, direction, class_l = preds["radius"], preds["direction"], preds["class_l"]

@@ -13,6 +13,12 @@ The `train-smart-tree` run (train.py:166-262 with conf/training.yaml): `main(arg
 [key=value ...]` loads `conf/training.yaml` (smart_tree_amd/config.py), trains with the epochs above and writes `config.yaml`,
 `metrics.jsonl`, `<run_name>_model_weights.pt` (each new best), `last.pt` (every epoch) and `captures/` into `run_dir`;
 `resume=<run_dir>` continues from that run's `last.pt`.  `StopPolicy` holds the best / early-stop / scheduler decisions.
+
+Data parallel (model/data_parallel.py, model/sync_bn.py): `train_epoch` / `eval_epoch(..., group=g)` take rank g's share of
+every global batch, synchronise BatchNorm (the model must have gone through `sync_bn.convert_sync_batchnorm`), weight the loss
+terms by the global row counts and all-reduce the gradients.  `python -m torch.distributed.run --nproc_per_node N -m
+smart_tree_amd.model.train ...` (or `run(cfg)` under an initialised group of more than one rank) trains that way; rank 0 writes
+the run's files, every rank its own trees' captures.  With one rank nothing changes.
 """
 from __future__ import annotations
 
@@ -28,10 +34,12 @@ from typing import List, NamedTuple
 
 import numpy as np
 import torch
+import torch.distributed as dist
 import yaml
 
 from ..config import apply_overrides, instantiate, load_yaml, resolve
 from ..data_types.cloud import Cloud
+from . import data_parallel as dp
 from .helper import get_batch, model_output_to_labelled_clds
 from .sparse import sparse_from_batch
 from .tracker import MetricsSink, total
@@ -41,8 +49,12 @@ CONF = Path(__file__).resolve().parents[1] / "conf" / "training.yaml"
 REQUIRED = ("directory", "json_path")
 
 
-def _batches(data_loader, device, fp16=False):
-    for (feats, targets), coords, mask, _ in data_loader:
+def _batches(data_loader, device, fp16=False, model=None):
+    for item in data_loader:
+        if item is None:  # data parallel: this rank owns no tree of the global batch
+            feats, coords, targets, mask = dp.empty_batch(model, device)
+        else:
+            (feats, targets), coords, mask, _ = item
         if fp16:  # get_batch(fp_16=True): the values rounded to half (the convolutions cast to half under autocast, exactly)
             feats, targets = feats.half(), targets.half()
         yield sparse_from_batch(feats.float(), coords, device=device), targets.to(device).float(), mask.to(device)
@@ -52,48 +64,78 @@ def _mean(sums, count):
     return {k: v / max(count, 1) for k, v in sums.items()}
 
 
-def train_epoch(data_loader, model, optimizer, loss_fn, device=torch.device("cuda"), *, fp16=False, scaler=None) -> dict:
+def _data_parallel(data_loader, model, loss_fn, group):
+    """The rank's shard of `data_loader`, after checking that the model and the loss can be reduced across ranks."""
+    dp.check_loss_fn(loss_fn)
+    if any(isinstance(m, torch.nn.modules.batchnorm._BatchNorm) for m in model.modules()):
+        raise ValueError("data-parallel training needs synchronised BatchNorm: call sync_bn.convert_sync_batchnorm(model, group) "
+                         "before building the optimiser")
+    return dp.shard_loader(data_loader, group)
+
+
+def train_epoch(data_loader, model, optimizer, loss_fn, device=torch.device("cuda"), *, fp16=False, scaler=None, group=None) -> dict:
     """One pass over `data_loader` with an optimiser step per batch (train.py:24-58); returns the mean of each loss term.
-    fp16=True: autocast to float16 and loss scaling through `scaler` (a torch.amp.GradScaler, required)."""
+    fp16=True: autocast to float16 and loss scaling through `scaler` (a torch.amp.GradScaler, required).
+    group: data parallel over that process group (module docstring); the returned means are the global batches'."""
     device = torch.device(device)
     if fp16 and scaler is None:
         raise ValueError("train_epoch(fp16=True) needs the run's GradScaler (scaler=...), the same one for every epoch")
+    if group is not None:
+        data_loader = _data_parallel(data_loader, model, loss_fn, group)
     model.train()
     sums, count = {}, 0
-    for sp_input, targets, mask in _batches(data_loader, device, fp16):
+    for sp_input, targets, mask in _batches(data_loader, device, fp16, model):
+        logged = None
         if fp16:
             with torch.autocast(device.type, dtype=torch.float16):
                 preds = model.forward(sp_input)
-                loss = loss_fn(preds, targets, mask)
+                if group is None:
+                    loss = loss_fn(preds, targets, mask)
+                else:
+                    loss, logged = dp.global_loss(loss_fn, preds, targets, mask, group)
                 total = sum(loss.values())
             assert total.dtype == torch.float32, total.dtype  # train.py:46
             scaler.scale(total).backward()
+            if group is not None:
+                dp.all_reduce_grads(model.parameters(), group)  # before the step: the same inf / NaN skip on every rank
             scaler.step(optimizer)
             scaler.update()
         else:
             preds = model.forward(sp_input)
-            loss = loss_fn(preds, targets, mask)
+            if group is None:
+                loss = loss_fn(preds, targets, mask)
+            else:
+                loss, logged = dp.global_loss(loss_fn, preds, targets, mask, group)
             sum(loss.values()).backward()
+            if group is not None:
+                dp.all_reduce_grads(model.parameters(), group)
             optimizer.step()
         optimizer.zero_grad()
-        for k, v in loss.items():
-            sums[k] = sums.get(k, 0.0) + float(v.detach())
+        for k, v in (logged or {k: float(v.detach()) for k, v in loss.items()}).items():
+            sums[k] = sums.get(k, 0.0) + v
         count += 1
     return _mean(sums, count)
 
 
 @torch.no_grad()
-def eval_epoch(data_loader, model, loss_fn, device=torch.device("cuda"), *, fp16=False) -> dict:
+def eval_epoch(data_loader, model, loss_fn, device=torch.device("cuda"), *, fp16=False, group=None) -> dict:
     """train.py:61-84: the losses in eval mode (running BatchNorm statistics), no gradients; the model is left in train mode.
-    fp16=True: under float16 autocast, as train_epoch."""
+    fp16=True: under float16 autocast, as train_epoch.  group: each rank evaluates its share of every global batch and the
+    per-batch values are the global count-weighted means."""
     device = torch.device(device)
+    if group is not None:
+        data_loader = _data_parallel(data_loader, model, loss_fn, group)
     model.eval()
     sums, count = {}, 0
-    for sp_input, targets, mask in _batches(data_loader, device, fp16):
+    for sp_input, targets, mask in _batches(data_loader, device, fp16, model):
         with torch.autocast(device.type, dtype=torch.float16, enabled=fp16):
-            loss = loss_fn(model.forward(sp_input), targets, mask)
-        for k, v in loss.items():
-            sums[k] = sums.get(k, 0.0) + float(v)
+            preds = model.forward(sp_input)
+            if group is None:
+                values = {k: float(v) for k, v in loss_fn(preds, targets, mask).items()}
+            else:
+                values = dp.global_loss(loss_fn, preds, targets, mask, group)[1]
+        for k, v in values.items():
+            sums[k] = sums.get(k, 0.0) + v
         count += 1
     model.train()
     return _mean(sums, count)
@@ -155,8 +197,8 @@ def load_training_config(overrides=()) -> dict:
     missing = [k for k in REQUIRED if cfg.get(k) in (None, "???", "")]
     if missing:
         raise ValueError(f"train-smart-tree: {' and '.join(missing)} not set: pass " + " ".join(f"{k}=..." for k in missing))
-    if cfg.get("device", "auto") == "auto":
-        cfg["device"] = "cuda:0" if torch.cuda.is_available() else "cpu"
+    if cfg.get("device", "auto") == "auto":  # under torchrun: this rank's GPU
+        cfg["device"] = f"cuda:{int(os.environ.get('LOCAL_RANK', 0))}" if torch.cuda.is_available() else "cpu"
     cfg = resolve(cfg)
     if cfg.get("resume"):
         cfg["run_dir"] = str(cfg["resume"])
@@ -191,24 +233,41 @@ def _save(obj, path: Path) -> None:
     os.replace(tmp, path)
 
 
-def _capture(run_dir: Path, epoch: int, loaders: dict, model, cfg, device) -> None:
+def _capture(run_dir: Path, epoch: int, loaders: dict, model, cfg, device, group=None) -> None:
     from ..util.file import save_cloud
 
     for split, loader in loaders.items():
+        if group is not None:  # each rank captures its own trees
+            loader = [b for b in dp.shard_loader(loader, group) if b is not None]
         out = run_dir / "captures" / f"epoch_{epoch}" / split
         out.mkdir(parents=True, exist_ok=True)
         for cloud in capture_clouds(loader, model, cfg["cmap"], fp16=cfg["fp16"], device=device):
             save_cloud(out / f"{Path(cloud.filename).stem}.npz", cloud)
 
 
-def run(cfg: dict) -> dict:
-    """train.py:166-262 on a resolved configuration (load_training_config).  Returns {"run_dir", "epochs", "best", "stopped"}."""
+def _gather_rng(group) -> list:
+    """Every rank's rng_state(), on every rank (rank 0 writes them)."""
+    states = [None] * dist.get_world_size(group)
+    dist.all_gather_object(states, rng_state(), group=group)
+    return states
+
+
+def run(cfg: dict, group=None) -> dict:
+    """train.py:166-262 on a resolved configuration (load_training_config).  Returns {"run_dir", "epochs", "best", "stopped"}.
+    Data parallel over `group`, or over the default process group when one with more than one rank is initialised."""
+    group = dp.default_group(group)
+    rank, world = dp.rank_world(group)
+    lead = rank == 0
     run_dir = Path(cfg["run_dir"])
     run_dir.mkdir(parents=True, exist_ok=True)
     device = torch.device(cfg["device"])
     fp16 = bool(cfg["fp16"])
-    log.info("run directory: %s, device: %s", run_dir, device)
-    (run_dir / "config.yaml").write_text(yaml.safe_dump(cfg, sort_keys=False))
+    log.info("run directory: %s, device: %s%s", run_dir, device, f", rank {rank} of {world}" if group is not None else "")
+    if group is not None:
+        cfg = {**cfg, "world_size": world}
+    if lead:
+        (run_dir / "config.yaml").write_text(yaml.safe_dump(cfg, sort_keys=False))
+    ep_kw = {"group": group} if group is not None else {}
 
     torch.manual_seed(42)
     torch.cuda.manual_seed_all(42)
@@ -218,61 +277,86 @@ def run(cfg: dict) -> dict:
     log.info("trees: %d train, %d validation, %d test", len(train_loader.dataset), len(val_loader.dataset),
              len(test_loader.dataset))
     model = instantiate(cfg["model"]).to(device).train()
+    if group is not None:
+        from .sync_bn import convert_sync_batchnorm
+
+        convert_sync_batchnorm(model, group)
     optimizer = instantiate(cfg["optimizer"], params=model.parameters())
     scheduler = instantiate(cfg["scheduler"], optimizer=optimizer)
     loss_fn = instantiate(cfg["loss_fn"])
     scaler = torch.amp.GradScaler(device.type, enabled=fp16)
     policy = StopPolicy(cfg["early_stop_epoch"], cfg["early_stop"], cfg["lr_decay"])
-    sink = MetricsSink(run_dir / "metrics.jsonl")
+    sink = MetricsSink(run_dir / "metrics.jsonl") if lead else None
     weights_path = run_dir / f"{cfg['run_name']}_model_weights.pt"
 
     start, stopped = 0, False
     if cfg.get("resume"):
         ck = torch.load(Path(cfg["resume"]) / "last.pt", map_location="cpu", weights_only=True)
+        if ck.get("world_size", 1) != world:
+            raise ValueError(f"resume: {cfg['resume']} was trained on {ck.get('world_size', 1)} rank(s) and this run has {world}: resume "
+                             "with the same number of ranks (each rank restores its own random state)")
         model.load_state_dict(ck["model"])
         optimizer.load_state_dict(ck["optimizer"])
         scheduler.load_state_dict(ck["scheduler"])
         scaler.load_state_dict(ck["scaler"])
         policy.best, policy.epochs_no_improve = ck["best"], ck["epochs_no_improve"]
         start, stopped = ck["epoch"] + 1, ck["stopped"]
-        set_rng_state(ck["rng"])
-        sink.truncate(start)
+        set_rng_state(ck["rng_ranks"][rank] if group is not None else ck["rng"])
+        if lead:
+            sink.truncate(start)
         log.info("resumed after epoch %d (best %.6g)%s", ck["epoch"], policy.best, ", which had stopped early" if stopped else "")
 
     epoch = start - 1
     for epoch in range(start, cfg["num_epoch"] if not stopped else start):
         t0 = time.perf_counter()
         lr = optimizer.param_groups[0]["lr"]
-        train = train_epoch(train_loader, model, optimizer, loss_fn, device, fp16=fp16, scaler=scaler)
-        val = eval_epoch(val_loader, model, loss_fn, device, fp16=fp16)
-        test = eval_epoch(test_loader, model, loss_fn, device, fp16=fp16)
+        train = train_epoch(train_loader, model, optimizer, loss_fn, device, fp16=fp16, scaler=scaler, **ep_kw)
+        val = eval_epoch(val_loader, model, loss_fn, device, fp16=fp16, **ep_kw)
+        test = eval_epoch(test_loader, model, loss_fn, device, fp16=fp16, **ep_kw)
         if cfg["capture_output"] > 0 and (epoch + 1) % cfg["capture_output"] == 0:
-            _capture(run_dir, epoch, {"test": test_loader, "validation": val_loader}, model, cfg, device)
+            _capture(run_dir, epoch, {"test": test_loader, "validation": val_loader}, model, cfg, device, group)
+        if group is not None:
+            dp.check_replicas(model, group)
         decision = policy.update(total(val))
         if decision.step_scheduler:
             scheduler.step(total(val))
-        if decision.save_best:
+        if decision.save_best and lead:
             _save({k: v.detach().cpu() for k, v in model.state_dict().items()}, weights_path)
         stopped = decision.stop
         seconds = time.perf_counter() - t0
-        sink.log({"lr": lr, "seconds": seconds, "best": policy.best}, step=epoch)
-        for name, means in (("train", train), ("validation", val), ("test", test)):
-            sink.log({name: {**means, "total": total(means)}}, step=epoch)
-        sink.commit()
+        if lead:
+            sink.log({"lr": lr, "seconds": seconds, "best": policy.best}, step=epoch)
+            for name, means in (("train", train), ("validation", val), ("test", test)):
+                sink.log({name: {**means, "total": total(means)}}, step=epoch)
+            sink.commit()
         log.info("epoch %d/%d: train %.4f, validation %.4f, test %.4f, lr %.3g, %.2f s%s", epoch + 1, cfg["num_epoch"], total(train),
                  total(val), total(test), lr, seconds, ", weights saved" if decision.save_best else "")
-        _save({"model": model.state_dict(), "optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(),
-               "scaler": scaler.state_dict(), "epoch": epoch, "best": policy.best,
-               "epochs_no_improve": policy.epochs_no_improve, "stopped": stopped, "rng": rng_state()}, run_dir / "last.pt")
+        state = {"model": model.state_dict(), "optimizer": optimizer.state_dict(), "scheduler": scheduler.state_dict(),
+                 "scaler": scaler.state_dict(), "epoch": epoch, "best": policy.best,
+                 "epochs_no_improve": policy.epochs_no_improve, "stopped": stopped, "rng": rng_state()}
+        if group is not None:
+            state.update(world_size=world, rng_ranks=_gather_rng(group))
+            dist.barrier(group)  # every rank has read the previous last.pt before it is replaced
+        if lead:
+            _save(state, run_dir / "last.pt")
         if stopped:
             log.info("training ended: validation total not improving for %d epochs", policy.epochs_no_improve)
             break
+    if group is not None:
+        dist.barrier(group)  # rank 0's files are complete when any rank returns
     return {"run_dir": run_dir, "epochs": epoch + 1, "best": policy.best, "stopped": stopped}
 
 
 def main(argv=None) -> dict:
+    """The run; under torchrun (WORLD_SIZE > 1) the process group is initialised from its environment first."""
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s: %(message)s")
-    return run(load_training_config(sys.argv[1:] if argv is None else argv))
+    cfg = load_training_config(sys.argv[1:] if argv is None else argv)
+    created = dp.init_from_env(cfg)
+    try:
+        return run(cfg)
+    finally:
+        if created:
+            dist.destroy_process_group()
 
 
 if __name__ == "__main__":

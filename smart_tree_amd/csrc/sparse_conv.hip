@@ -183,157 +183,80 @@ __global__ void __launch_bounds__(CONV_BLOCK) k_sparse_conv_any(const float* __r
     }
 }
 
+// The arguments every conv entry point takes, as the launchers pass them on (pointers untyped: the entry decides the storage types).
+struct ConvArgs {
+    const void* x0;
+    int c0;
+    const void* x1;
+    const int32_t* nbr;
+    int K;
+    int64_t n_out, nstride;
+    const void* w;
+    const float *scale, *shift;
+    const void* residual;
+    int relu;
+    void* y;
+    const int32_t* row_order;
+    hipStream_t stream;
+};
+
+// The checks the four entry points share; nstride arrives as the caller's nbr_stride (0 = n_out).
+static int conv_check_args(ConvArgs* a, int cin) {
+    if (a->nstride <= 0) a->nstride = a->n_out;
+    ST_REQUIRE(a->K >= 1 && (a->nbr != nullptr || a->K == 1), "conv: a NULL neighbour table means pointwise (K = 1)");
+    ST_REQUIRE(a->c0 > 0 && a->c0 <= cin && (a->c0 == cin || a->x1 != nullptr), "conv: bad concat split");
+    ST_REQUIRE((a->scale == nullptr) == (a->shift == nullptr), "conv: scale and shift go together");
+    return ST_OK;
+}
+
 template <int CIN, int COT, class TIN = float, class TOUT = float>
-static int conv_launch(const TIN* x0, int c0, const TIN* x1, const int32_t* nbr, int K, int64_t n_out, int64_t nstride, const float* w,
-                       int cout, const float* scale, const float* shift, const float* residual, int relu, TOUT* y,
-                       hipStream_t stream, const int32_t* row_order = nullptr) {
-    int64_t blocks = st_div_up(n_out, CONV_BLOCK) * (cout / COT);
-    hipLaunchKernelGGL((k_sparse_conv<CIN, COT, TIN, TOUT>), dim3((unsigned)blocks), dim3(CONV_BLOCK), 0, stream, x0, c0, x1, nbr, K,
-                       n_out, nstride, w, cout, scale, shift, residual, relu, y, row_order);
+static int conv_launch(const ConvArgs& a, int cout) {
+    int64_t blocks = st_div_up(a.n_out, CONV_BLOCK) * (cout / COT);
+    hipLaunchKernelGGL((k_sparse_conv<CIN, COT, TIN, TOUT>), dim3((unsigned)blocks), dim3(CONV_BLOCK), 0, a.stream, (const TIN*)a.x0, a.c0,
+                       (const TIN*)a.x1, a.nbr, a.K, a.n_out, a.nstride, (const float*)a.w, cout, a.scale, a.shift, (const float*)a.residual,
+                       a.relu, (TOUT*)a.y, a.row_order);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }
 
 // ------------------------------------------------------------------------- MFMA rule-GEMM ---
-// For Cin, Cout multiples of 16 the per-offset contraction [16 voxels x Cin] . [Cin x Cout] runs on the
-// matrix cores with v_mfma_f32_16x16x4_f32 (f32 in / f32 accumulate; NOT bit-identical to the vector kernel's fmaf chain -- measured in round 2: last-bit differences --
-// so a layer must use the same kernel family at every size,
-// cdna_hip_programming.md section 3), still output-stationary and atomics-free:
-//   wave   = MF_RT row tiles of 16 output voxels x all Cout (Cout/16 column tiles), accumulators in VGPRs
-//   A      = gathered input rows: lane (i = l&15, kg = l>>4) loads ONE float4 = channels 16c+4kg .. +3 of row i
-//            (a 64 B contiguous piece per row and instruction); register s of it feeds MFMA step s
-//   B      = W_k staged once per offset and workgroup in LDS in the matching order
-//            wp[k][c][kg][co][s] = W[k][16c + 4kg + s][co]  (host pre-permuted: a straight float4 copy),
-//            read with one ds_read_b128 per (c, column tile)
+// For Cin, Cout multiples of 16 the per-offset contraction [16 voxels x Cin] . [Cin x Cout] runs on the matrix cores, still
+// output-stationary and atomics-free.  One body (conv_rule_gemm) serves three operand policies -- f32, split-bf16, half -- that
+// say only how a lane turns a gathered row piece into an A fragment, where its B fragment sits in the pre-laid-out weights and
+// which matrix instruction(s) consume them.  Common to all:
+//   wave   = RT row tiles of 16 output voxels x all Cout (Cout/16 column tiles), accumulators in VGPRs
+//   A      = gathered input rows: lane (i = l&15, g = l>>4) loads channels CHUNK*c + (CHUNK/4)*g .. of row i, one contiguous
+//            piece per row and chunk c
+//   B      = a 16-byte vector per (step, chunk, plane, g, output column i), host pre-permuted into that order
 //   D      = lane l holds rows (l>>4)*4 + r, column l&15 of each 16x16 tile: epilogue = BN affine, residual,
 //            ReLU, 64 B row segments stored per instruction.
 typedef float st_v4f __attribute__((ext_vector_type(4)));
 #define MF_BLOCK 256
 
-// RT = row tiles (of 16 output voxels) per wave; LDSW = stage W_k through LDS (one copy per workgroup and
-// offset, two barriers) or let every lane fetch its B float4 straight from the L2-resident weights (no
-// barrier, loads free to run ahead of the MFMAs).
-template <int CIN, int COUT, int RT, bool LDSW>
-__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma(const float* __restrict__ x0, int c0, const float* __restrict__ x1,
-                                                               const int32_t* __restrict__ nbr, int K, int64_t n_out, int64_t nstride,
-                                                               const float* __restrict__ wp, const float* __restrict__ scale,
-                                                               const float* __restrict__ shift, const float* __restrict__ residual,
-                                                               int relu, float* __restrict__ y, const int32_t* __restrict__ row_order) {
-    constexpr int CT = COUT / 16, NC = CIN / 16;
-    __shared__ float4 wl[LDSW ? CIN * COUT / 4 : 1];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i16 = lane & 15, kg = lane >> 4;
-    const int64_t obase = ((int64_t)blockIdx.x * (MF_BLOCK / 64) + wave) * (16 * RT);
-    const int c1 = CIN - c0;
-    st_v4f acc[RT][CT];
-#pragma unroll
-    for (int t = 0; t < RT; t++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[t][ct] = st_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-
-    int64_t orow[RT];  // output row of tile position i16 (identity unless row_order is given)
-    uint32_t live[RT];
-#pragma unroll
-    for (int t = 0; t < RT; t++) {
-        const int64_t pos = obase + t * 16 + i16;
-        const int32_t entry = pos < n_out && row_order ? row_order[pos] : 0;
-        orow[t] = pos < n_out ? (row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos) : -1;
-        live[t] = conv_live_offsets(entry, K);
+// f32 operands: v_mfma_f32_16x16x4_f32 (f32 in / f32 accumulate; NOT bit-identical to the vector kernel's fmaf chain -- measured
+// in round 2: last-bit differences -- so a layer must use the same kernel family at every size, cdna_hip_programming.md section 3).
+//   A      = ONE float4 = channels 16c+4g .. +3 of row i (a 64 B contiguous piece per row and instruction); register s of it
+//            feeds MFMA step s
+//   B      = wp[k][c][g][co][s] = W[k][16c + 4g + s][co]  (host pre-permuted: sparse_ops.mfma_weight), one float4 per (c, column
+//            tile), either straight from the L2-resident weights or staged per offset in LDS (LDSW, see conv_rule_gemm)
+struct MfF32 {
+    typedef float T;         // storage of features, residual and output
+    typedef float4 W, A, B;  // 16-byte weight vector; A and B fragment of a lane
+    static constexpr int CHUNK = 16, PLANES = 1;  // input channels per chunk; weight planes per chunk
+    typedef float4 Row;
+    static __device__ __forceinline__ Row no_row() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    static __device__ __forceinline__ Row load_row(const T* row) { return *reinterpret_cast<const float4*>(row); }
+    static __device__ __forceinline__ A fragment(const Row& r) { return r; }
+    static __device__ __forceinline__ B load_b(const W* wc, int) { return *wc; }
+    static __device__ __forceinline__ void mma(const A& a, const B& b, st_v4f& d) {
+        d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, d, 0, 0, 0);
     }
-    for (int k = 0; k < K; k++) {
-        const float4* wsrc = reinterpret_cast<const float4*>(wp + (int64_t)k * CIN * COUT);
-        if (LDSW) {
-            __syncthreads();  // everyone is done with the previous offset's weights
-            for (int i = tid; i < CIN * COUT / 4; i += MF_BLOCK) wl[i] = wsrc[i];
-        }
-        int idx[RT];
-        bool any = false;
-#pragma unroll
-        for (int t = 0; t < RT; t++) {
-            idx[t] = orow[t] >= 0 && ((live[t] >> k) & 1u) ? (nbr ? nbr[(int64_t)k * nstride + orow[t]] : (int)orow[t]) : -1;
-            any = any || idx[t] >= 0;
-        }
-        if (LDSW) __syncthreads();
-        if (__ballot(any) == 0ull) continue;  // no voxel of this wave has a neighbour at offset k (wave-uniform)
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const int ci = 16 * c + 4 * kg;
-            float4 av[RT];
-#pragma unroll
-            for (int t = 0; t < RT; t++) {
-                av[t] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (idx[t] >= 0) {
-                    const float* row = ci < c0 ? x0 + (int64_t)idx[t] * c0 + ci : x1 + (int64_t)idx[t] * c1 + (ci - c0);
-                    av[t] = *reinterpret_cast<const float4*>(row);
-                }
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                const int wi = (c * 4 + kg) * COUT + ct * 16 + i16;
-                const float4 bv = LDSW ? wl[wi] : wsrc[wi];
-#pragma unroll
-                for (int t = 0; t < RT; t++) {
-                    acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].x, bv.x, acc[t][ct], 0, 0, 0);
-                    acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].y, bv.y, acc[t][ct], 0, 0, 0);
-                    acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].z, bv.z, acc[t][ct], 0, 0, 0);
-                    acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[t].w, bv.w, acc[t][ct], 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) {
-        const int ch = ct * 16 + i16;
-        const float sc = scale ? scale[ch] : 1.0f, sh = scale ? shift[ch] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < RT; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int64_t pos = obase + t * 16 + kg * 4 + r;
-                if (pos >= n_out) continue;
-                const int64_t o = row_order ? (int64_t)(row_order[pos] & CONV_ROW_MASK) : pos;
-                float v = acc[t][ct][r];
-                if (scale) v = fmaf(v, sc, sh);
-                if (residual) v += residual[o * COUT + ch];
-                if (relu) v = v > 0.0f ? v : 0.0f;
-                y[o * COUT + ch] = v;
-            }
-    }
-}
+};
 
-template <int CIN, int COUT, int RT, bool LDSW>
-static void conv_launch_mfma_v(const float* x0, int c0, const float* x1, const int32_t* nbr, int K, int64_t n_out, int64_t nstride, const float* wp,
-                               const float* scale, const float* shift, const float* residual, int relu, float* y,
-                               hipStream_t stream, const int32_t* row_order) {
-    const int64_t blocks = st_div_up(n_out, (MF_BLOCK / 64) * 16 * RT);
-    hipLaunchKernelGGL((k_sparse_conv_mfma<CIN, COUT, RT, LDSW>), dim3((unsigned)blocks), dim3(MF_BLOCK), 0, stream, x0, c0, x1,
-                       nbr, K, n_out, nstride, wp, scale, shift, residual, relu, y, row_order);
-}
-
-template <int CIN, int COUT>
-static int conv_launch_mfma(const float* x0, int c0, const float* x1, const int32_t* nbr, int K, int64_t n_out, int64_t nstride, const float* wp,
-                            const float* scale, const float* shift, const float* residual, int relu, float* y,
-                            hipStream_t stream, const int32_t* row_order, int variant) {
-    int v = variant;  // 0: by size (below); else RT | (LDSW << 4): tools/bench_conv.py times the variants
-    // measured on MI355X (tools/bench_conv.py, profiles/r02_conv_variants_batch8.txt): one row tile per wave with the weights
-    // straight from L2 wins while a level has too few rows to fill the chip (one cloud: <= 90k rows below level 0) and for the
-    // parity-ordered inverse convs; from ~150k rows on (a batch of clouds, the 5M-point cloud) two row tiles per wave with
-    // W_k staged once per workgroup in LDS is 5-20 % faster (B fragments reused, a quarter of the weight traffic from L2)
-    if (v == 0) v = (row_order == nullptr && n_out >= 150000) ? 18 : 1;
-#define MFMA_V(RT_, L_) conv_launch_mfma_v<CIN, COUT, RT_, L_>(x0, c0, x1, nbr, K, n_out, nstride, wp, scale, shift, residual, relu, y, stream, row_order)
-    switch (v) {
-        case 1: MFMA_V(1, false); break;
-        case 2: MFMA_V(2, false); break;
-        case 4: MFMA_V(4, false); break;
-        case 17: MFMA_V(1, true); break;
-        default: MFMA_V(2, true); break;
-    }
-#undef MFMA_V
-    ST_CHECK_LAUNCH();
-    return ST_OK;
-}
-
-// ------------------------------------------------------------- split-bf16 rule-GEMM (round 3) ---
+// ------------------------------------------------------------- split-bf16 operands (round 3) ---
 // The f32 matrix instruction runs at the vector rate (v_mfma_f32_16x16x4_f32: 32 cycles for 2048 flops), and the 32- and
 // 64-channel levels keep that pipe 49-68 % busy.  Here the SAME float32 features and weights are contracted on the bf16 pipe
 // (v_mfma_f32_16x16x32_bf16: ~17 cycles for 16384 flops) without giving up float32 accuracy: a float32 is cut into three bf16
@@ -347,6 +270,8 @@ static int conv_launch_mfma(const float* x0, int c0, const float* x1, const int3
 // tensor format, every other kernel is untouched.  Weights: host-side split into the same three planes, operand order
 //   wq[k][c][plane][g][co][e] = piece `plane` of W[k][32c + 8g + e][co]   (bf16, a 16-byte vector per (k, c, plane, g, co))
 // lane (i = l & 15, g = l >> 4) feeds channels 32c + 8g .. +7 of row i (A: two float4 loads) and of output column i (B).
+// B fragments come straight from the L2-resident planes (staging an offset's planes in LDS once per workgroup, two barriers per
+// offset, measured no faster at 16 clouds per launch set and 1.5x slower for the parity-ordered inverse convs).
 typedef __bf16 st_bf8 __attribute__((ext_vector_type(8)));
 struct StB3 { uint4 h, m, l; };
 // (upper halves of a1, a0) packed as two bf16: v_perm_b32 {a1.b3, a1.b2, a0.b3, a0.b2}
@@ -370,246 +295,66 @@ __device__ __forceinline__ StB3 b3_split8(float4 a, float4 b) {
 }
 __device__ __forceinline__ st_bf8 b3_bf8(uint4 v) { return __builtin_bit_cast(st_bf8, v); }
 
-template <int CIN, int COUT, int RT>
-__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_b3(const float* __restrict__ x0, int c0, const float* __restrict__ x1,
-                                                                  const int32_t* __restrict__ nbr, int K, int64_t n_out, int64_t nstride,
-                                                                  const uint4* __restrict__ wq, const float* __restrict__ scale,
-                                                                  const float* __restrict__ shift, const float* __restrict__ residual,
-                                                                  int relu, float* __restrict__ y, const int32_t* __restrict__ row_order) {
-    constexpr int CT = COUT / 16, NC = CIN / 32, WK = NC * 3 * 4 * COUT;  // 16-byte vectors of one offset's weights
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i16 = lane & 15, g = lane >> 4;
-    const int64_t obase = ((int64_t)blockIdx.x * (MF_BLOCK / 64) + wave) * (16 * RT);
-    const int c1 = CIN - c0;
-    st_v4f acc[RT][CT];
-#pragma unroll
-    for (int t = 0; t < RT; t++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[t][ct] = st_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    int64_t orow[RT];
-    uint32_t live[RT];
-#pragma unroll
-    for (int t = 0; t < RT; t++) {
-        const int64_t pos = obase + t * 16 + i16;
-        const int32_t entry = pos < n_out && row_order ? row_order[pos] : 0;
-        orow[t] = pos < n_out ? (row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos) : -1;
-        live[t] = conv_live_offsets(entry, K);
+struct MfB3 {
+    typedef float T;
+    typedef uint4 W;
+    typedef StB3 A;
+    struct B { st_bf8 h, m, l; };
+    static constexpr int CHUNK = 32, PLANES = 3;
+    struct Row { float4 lo4, hi4; };
+    static __device__ __forceinline__ Row no_row() { return Row{make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f)}; }
+    static __device__ __forceinline__ Row load_row(const T* row) { return Row{*reinterpret_cast<const float4*>(row), *reinterpret_cast<const float4*>(row + 4)}; }
+    static __device__ __forceinline__ A fragment(const Row& r) { return b3_split8(r.lo4, r.hi4); }
+    static __device__ __forceinline__ B load_b(const W* wc, int plane) { return B{b3_bf8(wc[0]), b3_bf8(wc[plane]), b3_bf8(wc[2 * plane])}; }
+    static __device__ __forceinline__ void mma(const A& a, const B& b, st_v4f& d) {
+        const st_bf8 ah = b3_bf8(a.h), am = b3_bf8(a.m), al = b3_bf8(a.l);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, b.h, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b.l, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b.m, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, b.h, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b.m, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, b.h, d, 0, 0, 0);
     }
-    for (int k = 0; k < K; k++) {
-        int idx[RT];
-        bool any = false;
-#pragma unroll
-        for (int t = 0; t < RT; t++) {
-            idx[t] = orow[t] >= 0 && ((live[t] >> k) & 1u) ? (nbr ? nbr[(int64_t)k * nstride + orow[t]] : (int)orow[t]) : -1;
-            any = any || idx[t] >= 0;
-        }
-        if (__ballot(any) == 0ull) continue;  // no voxel of this wave has a neighbour at offset k (wave-uniform)
-        // B fragments straight from the L2-resident planes (staging an offset's planes in LDS once per workgroup, two barriers per
-        // offset, measured no faster at 16 clouds per launch set and 1.5x slower for the parity-ordered inverse convs)
-        const uint4* wk = wq + (int64_t)k * WK;
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            const int ci = 32 * c + 8 * g;
-            StB3 a[RT];
-#pragma unroll
-            for (int t = 0; t < RT; t++) {
-                float4 lo4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi4 = lo4;
-                if (idx[t] >= 0) {
-                    const float* row = ci < c0 ? x0 + (int64_t)idx[t] * c0 + ci : x1 + (int64_t)idx[t] * c1 + (ci - c0);
-                    lo4 = *reinterpret_cast<const float4*>(row);
-                    hi4 = *reinterpret_cast<const float4*>(row + 4);
-                }
-                a[t] = b3_split8(lo4, hi4);
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ct++) {
-                const uint4* wc = wk + ((int64_t)(c * 3) * 4 + g) * COUT + ct * 16 + i16;  // plane stride = 4 * COUT
-                const st_bf8 bh = b3_bf8(wc[0]), bm = b3_bf8(wc[4 * COUT]), bl = b3_bf8(wc[8 * COUT]);
-#pragma unroll
-                for (int t = 0; t < RT; t++) {
-                    const st_bf8 ah = b3_bf8(a[t].h), am = b3_bf8(a[t].m), al = b3_bf8(a[t].l);
-                    st_v4f d = acc[t][ct];
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, d, 0, 0, 0);
-                    acc[t][ct] = d;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) {
-        const int ch = ct * 16 + i16;
-        const float sc = scale ? scale[ch] : 1.0f, sh = scale ? shift[ch] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < RT; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int64_t pos = obase + t * 16 + g * 4 + r;
-                if (pos >= n_out) continue;
-                const int64_t o = row_order ? (int64_t)(row_order[pos] & CONV_ROW_MASK) : pos;
-                float v = acc[t][ct][r];
-                if (scale) v = fmaf(v, sc, sh);
-                if (residual) v += residual[o * COUT + ch];
-                if (relu) v = v > 0.0f ? v : 0.0f;
-                y[o * COUT + ch] = v;
-            }
-    }
-}
+};
 
-// Sixteen input channels (the submanifold and strided convs of level 1): a 32-deep instruction takes TWO kernel offsets at once --
-// lanes g = 0, 1 feed channels 8g .. +7 of the row at offset 2j, lanes g = 2, 3 those of the row at offset 2j + 1, and the B operand
-// stacks W_{2j} on W_{2j+1} (zeros behind an odd last offset): wq[j][plane][g][co][e] = piece of W[2j + (g >> 1)][8 (g & 1) + e][co].
-template <int COUT, int RT>
-__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_b3_c16(const float* __restrict__ x, const int32_t* __restrict__ nbr, int K,
-                                                                      int64_t n_out, int64_t nstride, const uint4* __restrict__ wq,
-                                                                      const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                      const float* __restrict__ residual, int relu, float* __restrict__ y,
-                                                                      const int32_t* __restrict__ row_order) {
-    constexpr int CT = COUT / 16, WK = 3 * 4 * COUT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i16 = lane & 15, g = lane >> 4;
-    const int64_t obase = ((int64_t)blockIdx.x * (MF_BLOCK / 64) + wave) * (16 * RT);
-    st_v4f acc[RT][CT];
-#pragma unroll
-    for (int t = 0; t < RT; t++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[t][ct] = st_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    int64_t orow[RT];
-    uint32_t live[RT];
-#pragma unroll
-    for (int t = 0; t < RT; t++) {
-        const int64_t pos = obase + t * 16 + i16;
-        const int32_t entry = pos < n_out && row_order ? row_order[pos] : 0;
-        orow[t] = pos < n_out ? (row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos) : -1;
-        live[t] = conv_live_offsets(entry, K);
-    }
-    const int ch = 8 * (g & 1);
-    for (int j = 0; 2 * j < K; j++) {
-        const int k = 2 * j + (g >> 1);  // this lane's offset of the pair
-        int idx[RT];
-        bool any = false;
-#pragma unroll
-        for (int t = 0; t < RT; t++) {
-            idx[t] = k < K && orow[t] >= 0 && ((live[t] >> k) & 1u) ? (nbr ? nbr[(int64_t)k * nstride + orow[t]] : (int)orow[t]) : -1;
-            any = any || idx[t] >= 0;
-        }
-        if (__ballot(any) == 0ull) continue;  // neither offset of the pair has a neighbour in this wave (wave-uniform)
-        StB3 a[RT];
-#pragma unroll
-        for (int t = 0; t < RT; t++) {
-            float4 lo4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), hi4 = lo4;
-            if (idx[t] >= 0) {
-                const float* row = x + (int64_t)idx[t] * 16 + ch;
-                lo4 = *reinterpret_cast<const float4*>(row);
-                hi4 = *reinterpret_cast<const float4*>(row + 4);
-            }
-            a[t] = b3_split8(lo4, hi4);
-        }
-        const uint4* wk = wq + (int64_t)j * WK;
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
-            const uint4* wc = wk + (int64_t)g * COUT + ct * 16 + i16;  // plane stride = 4 * COUT
-            const st_bf8 bh = b3_bf8(wc[0]), bm = b3_bf8(wc[4 * COUT]), bl = b3_bf8(wc[8 * COUT]);
-#pragma unroll
-            for (int t = 0; t < RT; t++) {
-                const st_bf8 ah = b3_bf8(a[t].h), am = b3_bf8(a[t].m), al = b3_bf8(a[t].l);
-                st_v4f d = acc[t][ct];
-                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh, d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl, d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bm, d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bh, d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bm, d, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh, d, 0, 0, 0);
-                acc[t][ct] = d;
-            }
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) {
-        const int co = ct * 16 + i16;
-        const float sc = scale ? scale[co] : 1.0f, sh = scale ? shift[co] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < RT; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int64_t pos = obase + t * 16 + g * 4 + r;
-                if (pos >= n_out) continue;
-                const int64_t o = row_order ? (int64_t)(row_order[pos] & CONV_ROW_MASK) : pos;
-                float v = acc[t][ct][r];
-                if (scale) v = fmaf(v, sc, sh);
-                if (residual) v += residual[o * COUT + co];
-                if (relu) v = v > 0.0f ? v : 0.0f;
-                y[o * COUT + co] = v;
-            }
-    }
-}
-
-// Same contract as st_sparse_conv_mfma_fwd with the weights as three bf16 planes (see above; smart_tree_amd/model/sparse_ops.py
-// b3_weight).  Needs Cin % 32 == 0, Cout % 16 == 0 and a concat split that is a multiple of 8.  variant: 0 = by size, 1 / 2 = row
-// tiles per wavefront.
-extern "C" int st_sparse_conv_b3_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
-                                     const void* wq, int cout, const float* scale, const float* shift, const float* residual,
-                                     int relu, float* y, const int32_t* row_order, void* stream_, int64_t nbr_stride, int variant) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t nstride = nbr_stride > 0 ? nbr_stride : n_out;
-    ST_REQUIRE(K >= 1 && (nbr != nullptr || K == 1), "conv: a NULL neighbour table means pointwise (K = 1)");
-    ST_REQUIRE(c0 > 0 && c0 <= cin && (c0 == cin || x1 != nullptr), "conv: bad concat split");
-    ST_REQUIRE((scale == nullptr) == (shift == nullptr), "conv: scale and shift go together");
-    ST_REQUIRE((cin % 32 == 0 || (cin == 16 && c0 == cin)) && cout % 16 == 0 && c0 % 8 == 0,
-               "conv(b3): Cin % 32 (or Cin = 16 without concat), Cout % 16 and a concat split % 8 are required");
-    if (n_out <= 0) return ST_OK;
-    if (cin == 16) {  // two kernel offsets per instruction; wq = b3_weight's pair layout [ceil(K/2)][3][4][Cout][8]
-        const int rt16 = variant == 1 || variant == 2 ? variant : (n_out >= (row_order == nullptr ? 56000 : 300000) ? 2 : 1);
-#define B3_LAUNCH16(CO, RT_)                                                                                                            \
-    hipLaunchKernelGGL((k_sparse_conv_mfma_b3_c16<CO, RT_>), dim3((unsigned)st_div_up(n_out, (MF_BLOCK / 64) * 16 * RT_)), dim3(MF_BLOCK), 0, \
-                       stream, x0, nbr, K, n_out, nstride, (const uint4*)wq, scale, shift, residual, relu, y, row_order)
-        if (cout == 16) { if (rt16 == 2) B3_LAUNCH16(16, 2); else B3_LAUNCH16(16, 1); }
-        else if (cout == 32) { if (rt16 == 2) B3_LAUNCH16(32, 2); else B3_LAUNCH16(32, 1); }
-        else { st_set_error("conv(b3): no kernel instance for cin=16 cout=%d", cout); return ST_ERR_INVALID; }
-#undef B3_LAUNCH16
-        ST_CHECK_LAUNCH();
-        return ST_OK;
-    }
-    // measured on MI355X (tools/bench_conv.py at 1 / 4 / 16 clouds per launch set, profiles/r03_conv_layers_b3.txt): two row tiles per
-    // wavefront (each B fragment feeds two tiles) win from ~56k rows on, for the parity-ordered inverse convs from ~300k; below, one
-    // tile per wavefront gives the chip twice the wavefronts.  Both compute a row with the same instruction sequence: same bits.
-    const int rt = variant == 1 || variant == 2 ? variant : (n_out >= (row_order == nullptr ? 56000 : 300000) ? 2 : 1);
-#define B3_LAUNCH(CI, CO, RT_)                                                                                                          \
-    hipLaunchKernelGGL((k_sparse_conv_mfma_b3<CI, CO, RT_>), dim3((unsigned)st_div_up(n_out, (MF_BLOCK / 64) * 16 * RT_)), dim3(MF_BLOCK), 0, \
-                       stream, x0, c0, x1, nbr, K, n_out, nstride, (const uint4*)wq, scale, shift, residual, relu, y, row_order)
-#define B3_CASE(CI, CO)                                                  \
-    if (cin == CI && cout == CO) {                                       \
-        if (rt == 2) B3_LAUNCH(CI, CO, 2); else B3_LAUNCH(CI, CO, 1);    \
-        ST_CHECK_LAUNCH();                                               \
-        return ST_OK;                                                    \
-    }
-    B3_CASE(32, 16)
-    B3_CASE(32, 32)
-    B3_CASE(32, 64)
-    B3_CASE(64, 32)
-    B3_CASE(64, 64)
-#undef B3_CASE
-#undef B3_LAUNCH
-    st_set_error("conv(b3): no kernel instance for cin=%d cout=%d", cin, cout);
-    return ST_ERR_INVALID;
-}
-
-// fp16 rule-GEMM (config 5): features and weights in half precision, gfx950's 32-deep v_mfma_f32_16x16x32_f16 with float32
-// accumulation, for Cin % 32 == 0, with one or two row tiles per wavefront: lane (i = l & 15, g = l >> 4) feeds channels 32c + 8g .. +7
-// of row i (ONE 16-byte load) and of output column i; weights in the order wp[k][c][g][co][e] = W[k][32c + 8g + e][co] (half;
-// sparse_ops.mfma_weight32).  BatchNorm affine / residual / ReLU in float32, one rounding on the store.
+// Half operands (config 5): features and weights in half precision, gfx950's 32-deep v_mfma_f32_16x16x32_f16 with float32
+// accumulation: lane (i = l & 15, g = l >> 4) feeds channels 32c + 8g .. +7 of row i (ONE 16-byte load) and of output column i;
+// weights in the order wp[k][c][g][co][e] = W[k][32c + 8g + e][co] (half; sparse_ops.mfma_weight32).  BatchNorm affine / residual /
+// ReLU in float32, one rounding on the store.
 typedef _Float16 st_v8h __attribute__((ext_vector_type(8)));
-template <int CIN, int COUT, int RT>
-__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_f16x(const st_h* __restrict__ x0, int c0, const st_h* __restrict__ x1,
-                                                                    const int32_t* __restrict__ nbr, int K, int64_t n_out, int64_t nstride,
-                                                                    const st_v8h* __restrict__ wp, const float* __restrict__ scale,
-                                                                    const float* __restrict__ shift, const st_h* __restrict__ residual,
-                                                                    int relu, st_h* __restrict__ y, const int32_t* __restrict__ row_order) {
-    constexpr int CT = COUT / 16, NC = CIN / 32;
+struct MfF16 {
+    typedef st_h T;
+    typedef st_v8h W, A, B;
+    static constexpr int CHUNK = 32, PLANES = 1;
+    typedef st_v8h Row;
+    static __device__ __forceinline__ Row no_row() { return Row{}; }
+    static __device__ __forceinline__ Row load_row(const T* row) { return *reinterpret_cast<const st_v8h*>(row); }
+    static __device__ __forceinline__ A fragment(const Row& r) { return r; }
+    static __device__ __forceinline__ B load_b(const W* wc, int) { return *wc; }
+    static __device__ __forceinline__ void mma(const A& a, const B& b, st_v4f& d) { d = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, d, 0, 0, 0); }
+};
+
+#define MF_PARAMS(T, W)                                                                                                               \
+    const T *__restrict__ x0, int c0, const T *__restrict__ x1, const int32_t *__restrict__ nbr, int K, int64_t n_out, int64_t nstride, \
+        const W *__restrict__ w, const float *__restrict__ scale, const float *__restrict__ shift, const T *__restrict__ residual,     \
+        int relu, T *__restrict__ y, const int32_t *__restrict__ row_order
+#define MF_ARGS x0, c0, x1, nbr, K, n_out, nstride, w, scale, shift, residual, relu, y, row_order
+
+// The rule-GEMM.  A step of the K loop is one kernel offset; with sixteen input channels and a 32-deep instruction (PAIR) it is
+// TWO offsets at once -- lanes g = 0, 1 feed channels 8g .. +7 of the row at offset 2j, lanes g = 2, 3 those of the row at offset
+// 2j + 1, and the B operand stacks W_{2j} on W_{2j+1} (zeros behind an odd last offset; no concat):
+// wq[j][plane][g][co][e] = piece of W[2j + (g >> 1)][8 (g & 1) + e][co] (b3_weight, mfma_weight16_half).
+// RT = row tiles (of 16 output voxels) per wave; LDSW = stage a step's weights through LDS (one copy per workgroup and
+// offset, two barriers) or let every lane fetch its B fragment straight from the L2-resident weights (no
+// barrier, loads free to run ahead of the MFMAs).
+template <class OP, int CIN, int COUT, int RT, bool LDSW>
+__device__ __forceinline__ void conv_rule_gemm(MF_PARAMS(typename OP::T, typename OP::W)) {
+    typedef typename OP::T T;
+    typedef typename OP::W W;
+    constexpr bool PAIR = CIN == 16 && OP::CHUNK == 32;
+    constexpr int CT = COUT / 16, NC = PAIR ? 1 : CIN / OP::CHUNK, LCH = OP::CHUNK / 4;
+    constexpr int PLANE = 4 * COUT, WSTEP = NC * OP::PLANES * PLANE;  // 16-byte vectors of one plane / one step's weights
+    __shared__ W wl[LDSW ? WSTEP : 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i16 = lane & 15, g = lane >> 4;
     const int64_t obase = ((int64_t)blockIdx.x * (MF_BLOCK / 64) + wave) * (16 * RT);
@@ -619,7 +364,8 @@ __global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_f16x(const st_h* 
     for (int t = 0; t < RT; t++)
 #pragma unroll
         for (int ct = 0; ct < CT; ct++) acc[t][ct] = st_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    int64_t orow[RT];
+
+    int64_t orow[RT];  // output row of tile position i16 (identity unless row_order is given)
     uint32_t live[RT];
 #pragma unroll
     for (int t = 0; t < RT; t++) {
@@ -628,33 +374,40 @@ __global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_f16x(const st_h* 
         orow[t] = pos < n_out ? (row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos) : -1;
         live[t] = conv_live_offsets(entry, K);
     }
-    for (int k = 0; k < K; k++) {
+    for (int j = 0; (PAIR ? 2 * j : j) < K; j++) {
+        const int k = PAIR ? 2 * j + (g >> 1) : j;  // this lane's offset (of the pair)
+        if (LDSW) {
+            __syncthreads();  // everyone is done with the previous offset's weights
+            for (int i = tid; i < WSTEP; i += MF_BLOCK) wl[i] = w[(int64_t)j * WSTEP + i];
+        }
         int idx[RT];
         bool any = false;
 #pragma unroll
         for (int t = 0; t < RT; t++) {
-            idx[t] = orow[t] >= 0 && ((live[t] >> k) & 1u) ? (nbr ? nbr[(int64_t)k * nstride + orow[t]] : (int)orow[t]) : -1;
+            idx[t] = (!PAIR || k < K) && orow[t] >= 0 && ((live[t] >> k) & 1u) ? (nbr ? nbr[(int64_t)k * nstride + orow[t]] : (int)orow[t]) : -1;
             any = any || idx[t] >= 0;
         }
-        if (__ballot(any) == 0ull) continue;  // no voxel of this wave has a neighbour at offset k (wave-uniform)
-        const st_v8h* wk = wp + (int64_t)k * NC * 4 * COUT;
+        if (LDSW) __syncthreads();
+        if (__ballot(any) == 0ull) continue;  // no voxel of this wave has a neighbour at this step's offset(s) (wave-uniform)
+        const W* wb = LDSW ? wl : w + (int64_t)j * WSTEP;
 #pragma unroll
         for (int c = 0; c < NC; c++) {
-            const int ci = 32 * c + 8 * g;
-            st_v8h a[RT];
+            const int ci = PAIR ? LCH * (g & 1) : OP::CHUNK * c + LCH * g;
+            typename OP::A a[RT];
 #pragma unroll
             for (int t = 0; t < RT; t++) {
-                a[t] = st_v8h{(st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f};
+                typename OP::Row r = OP::no_row();
                 if (idx[t] >= 0) {
-                    const st_h* row = ci < c0 ? x0 + (int64_t)idx[t] * c0 + ci : x1 + (int64_t)idx[t] * c1 + (ci - c0);
-                    a[t] = *reinterpret_cast<const st_v8h*>(row);
+                    const T* row = PAIR ? x0 + (int64_t)idx[t] * CIN + ci : ci < c0 ? x0 + (int64_t)idx[t] * c0 + ci : x1 + (int64_t)idx[t] * c1 + (ci - c0);
+                    r = OP::load_row(row);
                 }
+                a[t] = OP::fragment(r);
             }
 #pragma unroll
             for (int ct = 0; ct < CT; ct++) {
-                const st_v8h b = wk[((int64_t)c * 4 + g) * COUT + ct * 16 + i16];
+                const typename OP::B b = OP::load_b(wb + (c * OP::PLANES * 4 + g) * COUT + ct * 16 + i16, PLANE);
 #pragma unroll
-                for (int t = 0; t < RT; t++) acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], b, acc[t][ct], 0, 0, 0);
+                for (int t = 0; t < RT; t++) OP::mma(a[t], b, acc[t][ct]);
             }
         }
     }
@@ -673,76 +426,93 @@ __global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_f16x(const st_h* 
                 if (scale) v = fmaf(v, sc, sh);
                 if (residual) v += (float)residual[o * COUT + ch];
                 if (relu) v = v > 0.0f ? v : 0.0f;
-                y[o * COUT + ch] = (st_h)v;
+                y[o * COUT + ch] = (T)v;
             }
     }
 }
 
-// ... and for 16 input channels two kernel offsets per instruction (lanes g = 0, 1: the row at offset 2j, g = 2, 3: at 2j + 1; B stacks
-// W_2j on W_2j+1, zeros behind an odd last offset: mfma_weight16_half lays the pairs out as 32-channel chunks).
+// The kernels: one name per operand policy and step mode (profiles and tools match kernel traces by these names).
+template <int CIN, int COUT, int RT, bool LDSW>
+__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma(MF_PARAMS(float, float4)) { conv_rule_gemm<MfF32, CIN, COUT, RT, LDSW>(MF_ARGS); }
+template <int CIN, int COUT, int RT>
+__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_b3(MF_PARAMS(float, uint4)) { conv_rule_gemm<MfB3, CIN, COUT, RT, false>(MF_ARGS); }
 template <int COUT, int RT>
-__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_f16x_c16(const st_h* __restrict__ x, const int32_t* __restrict__ nbr, int K,
-                                                                        int64_t n_out, int64_t nstride, const st_v8h* __restrict__ wp,
-                                                                        const float* __restrict__ scale, const float* __restrict__ shift,
-                                                                        const st_h* __restrict__ residual, int relu, st_h* __restrict__ y,
-                                                                        const int32_t* __restrict__ row_order) {
-    constexpr int CT = COUT / 16;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int i16 = lane & 15, g = lane >> 4;
-    const int64_t obase = ((int64_t)blockIdx.x * (MF_BLOCK / 64) + wave) * (16 * RT);
-    st_v4f acc[RT][CT];
-#pragma unroll
-    for (int t = 0; t < RT; t++)
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) acc[t][ct] = st_v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    int64_t orow[RT];
-    uint32_t live[RT];
-#pragma unroll
-    for (int t = 0; t < RT; t++) {
-        const int64_t pos = obase + t * 16 + i16;
-        const int32_t entry = pos < n_out && row_order ? row_order[pos] : 0;
-        orow[t] = pos < n_out ? (row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos) : -1;
-        live[t] = conv_live_offsets(entry, K);
+__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_b3_c16(MF_PARAMS(float, uint4)) { conv_rule_gemm<MfB3, 16, COUT, RT, false>(MF_ARGS); }
+template <int CIN, int COUT, int RT>
+__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_f16x(MF_PARAMS(st_h, st_v8h)) { conv_rule_gemm<MfF16, CIN, COUT, RT, false>(MF_ARGS); }
+template <int COUT, int RT>
+__global__ void __launch_bounds__(MF_BLOCK) k_sparse_conv_mfma_f16x_c16(MF_PARAMS(st_h, st_v8h)) { conv_rule_gemm<MfF16, 16, COUT, RT, false>(MF_ARGS); }
+
+template <class T, class W>
+using mf_kernel_t = void (*)(MF_PARAMS(T, W));
+// the split-bf16 / half kernel of a shape: the pair kernel for sixteen input channels
+template <int CIN, int COUT, int RT>
+static mf_kernel_t<float, uint4> b3_kernel() {
+    if constexpr (CIN == 16) return k_sparse_conv_mfma_b3_c16<COUT, RT>;
+    else return k_sparse_conv_mfma_b3<CIN, COUT, RT>;
+}
+template <int CIN, int COUT, int RT>
+static mf_kernel_t<st_h, st_v8h> f16x_kernel() {
+    if constexpr (CIN == 16) return k_sparse_conv_mfma_f16x_c16<COUT, RT>;
+    else return k_sparse_conv_mfma_f16x<CIN, COUT, RT>;
+}
+
+template <class T, class W>
+static int mf_launch(mf_kernel_t<T, W> kernel, int rt, const ConvArgs& a) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)st_div_up(a.n_out, (MF_BLOCK / 64) * 16 * rt)), dim3(MF_BLOCK), 0, a.stream, (const T*)a.x0, a.c0,
+                       (const T*)a.x1, a.nbr, a.K, a.n_out, a.nstride, (const W*)a.w, a.scale, a.shift, (const T*)a.residual, a.relu, (T*)a.y,
+                       a.row_order);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
+}
+
+// Row tiles per wavefront of the split-bf16 and half kernels.  Measured on MI355X (tools/bench_conv.py at 1 / 4 / 16 clouds per
+// launch set, profiles/r03_conv_layers_b3.txt): two row tiles per wavefront (each B fragment feeds two tiles) win from ~56k rows
+// on, for the parity-ordered inverse convs from ~300k; below, one tile per wavefront gives the chip twice the wavefronts.  Both
+// compute a row with the same instruction sequence: same bits.
+static int conv_row_tiles(const ConvArgs& a) { return a.n_out >= (a.row_order == nullptr ? 56000 : 300000) ? 2 : 1; }
+
+template <int CIN, int COUT>
+static int conv_launch_mfma(const ConvArgs& a, int v) {
+    // v = 0: by size (below); else RT | (LDSW << 4): tools/bench_conv.py times the variants
+    // measured on MI355X (tools/bench_conv.py, profiles/r02_conv_variants_batch8.txt): one row tile per wave with the weights
+    // straight from L2 wins while a level has too few rows to fill the chip (one cloud: <= 90k rows below level 0) and for the
+    // parity-ordered inverse convs; from ~150k rows on (a batch of clouds, the 5M-point cloud) two row tiles per wave with
+    // W_k staged once per workgroup in LDS is 5-20 % faster (B fragments reused, a quarter of the weight traffic from L2)
+    if (v == 0) v = (a.row_order == nullptr && a.n_out >= 150000) ? 18 : 1;
+    switch (v) {
+        case 1: return mf_launch(k_sparse_conv_mfma<CIN, COUT, 1, false>, 1, a);
+        case 2: return mf_launch(k_sparse_conv_mfma<CIN, COUT, 2, false>, 2, a);
+        case 4: return mf_launch(k_sparse_conv_mfma<CIN, COUT, 4, false>, 4, a);
+        case 17: return mf_launch(k_sparse_conv_mfma<CIN, COUT, 1, true>, 1, a);
+        default: return mf_launch(k_sparse_conv_mfma<CIN, COUT, 2, true>, 2, a);
     }
-    const int ch = 8 * (g & 1);
-    for (int j = 0; 2 * j < K; j++) {
-        const int k = 2 * j + (g >> 1);  // this lane's offset of the pair
-        bool any = false;
-        st_v8h a[RT];
-#pragma unroll
-        for (int t = 0; t < RT; t++) {
-            const int idx = k < K && orow[t] >= 0 && ((live[t] >> k) & 1u) ? (nbr ? nbr[(int64_t)k * nstride + orow[t]] : (int)orow[t]) : -1;
-            any = any || idx >= 0;
-            a[t] = st_v8h{(st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f, (st_h)0.0f};
-            if (idx >= 0) a[t] = *reinterpret_cast<const st_v8h*>(x + (int64_t)idx * 16 + ch);
-        }
-        if (__ballot(any) == 0ull) continue;  // neither offset of the pair has a neighbour in this wave (wave-uniform)
-        const st_v8h* wk = wp + (int64_t)j * 4 * COUT;
-#pragma unroll
-        for (int ct = 0; ct < CT; ct++) {
-            const st_v8h b = wk[(int64_t)g * COUT + ct * 16 + i16];
-#pragma unroll
-            for (int t = 0; t < RT; t++) acc[t][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[t], b, acc[t][ct], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int ct = 0; ct < CT; ct++) {
-        const int co = ct * 16 + i16;
-        const float sc = scale ? scale[co] : 1.0f, sh = scale ? shift[co] : 0.0f;
-#pragma unroll
-        for (int t = 0; t < RT; t++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int64_t pos = obase + t * 16 + g * 4 + r;
-                if (pos >= n_out) continue;
-                const int64_t o = row_order ? (int64_t)(row_order[pos] & CONV_ROW_MASK) : pos;
-                float v = acc[t][ct][r];
-                if (scale) v = fmaf(v, sc, sh);
-                if (residual) v += (float)residual[o * COUT + co];
-                if (relu) v = v > 0.0f ? v : 0.0f;
-                y[o * COUT + co] = (st_h)v;
-            }
-    }
+}
+
+// Same contract as st_sparse_conv_mfma_fwd with the weights as three bf16 planes (see above; smart_tree_amd/model/sparse_ops.py
+// b3_weight: for Cin = 16 the pair layout [ceil(K/2)][3][4][Cout][8]).  Needs Cin % 32 == 0, Cout % 16 == 0 and a concat split
+// that is a multiple of 8.  variant: 0 = by size, 1 / 2 = row tiles per wavefront.
+extern "C" int st_sparse_conv_b3_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                                     const void* wq, int cout, const float* scale, const float* shift, const float* residual,
+                                     int relu, float* y, const int32_t* row_order, void* stream_, int64_t nbr_stride, int variant) {
+    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, wq, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_};
+    ST_TRY(conv_check_args(&a, cin));
+    ST_REQUIRE((cin % 32 == 0 || (cin == 16 && c0 == cin)) && cout % 16 == 0 && c0 % 8 == 0,
+               "conv(b3): Cin % 32 (or Cin = 16 without concat), Cout % 16 and a concat split % 8 are required");
+    if (n_out <= 0) return ST_OK;
+    const int rt = variant == 1 || variant == 2 ? variant : conv_row_tiles(a);
+#define B3_CASE(CI, CO) \
+    if (cin == CI && cout == CO) return rt == 2 ? mf_launch(b3_kernel<CI, CO, 2>(), 2, a) : mf_launch(b3_kernel<CI, CO, 1>(), 1, a);
+    B3_CASE(16, 16)
+    B3_CASE(16, 32)
+    B3_CASE(32, 16)
+    B3_CASE(32, 32)
+    B3_CASE(32, 64)
+    B3_CASE(64, 32)
+    B3_CASE(64, 64)
+#undef B3_CASE
+    st_set_error("conv(b3): no kernel instance for cin=%d cout=%d", cin, cout);
+    return ST_ERR_INVALID;
 }
 
 // Half-precision storage variants of the two calls above (config 5).  in_half / out_half say which side is fp16:
@@ -755,58 +525,30 @@ extern "C" int st_sparse_conv_f16_fwd(const void* x0, int c0, const void* x1, in
                                       const void* w, int cout, const float* scale, const float* shift, const void* residual,
                                       int relu, void* y, int in_half, int out_half, const int32_t* row_order, void* stream_,
                                       int64_t nbr_stride) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t nstride = nbr_stride > 0 ? nbr_stride : n_out;
-    ST_REQUIRE(K >= 1 && (nbr != nullptr || K == 1), "conv: a NULL neighbour table means pointwise (K = 1)");
-    ST_REQUIRE(c0 > 0 && c0 <= cin && (c0 == cin || x1 != nullptr), "conv: bad concat split");
-    ST_REQUIRE((scale == nullptr) == (shift == nullptr), "conv: scale and shift go together");
+    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, w, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_};
+    ST_TRY(conv_check_args(&a, cin));
     ST_REQUIRE(in_half || out_half, "conv(f16): neither side is half precision -- use st_sparse_conv_fwd");
     if (n_out <= 0) return ST_OK;
     if (in_half && out_half) {
         ST_REQUIRE(cin % 16 == 0 && cout % 16 == 0 && c0 % 16 == 0, "conv(f16): channels and concat split must be multiples of 16");
-        if (cin == 16 && c0 == cin && (cout == 16 || cout == 32)) {  // two kernel offsets per 32-deep instruction (weights: mfma_weight16_half)
-            const int rt16 = n_out >= (row_order == nullptr ? 56000 : 300000) ? 2 : 1;
-#define F16C_LAUNCH(CO, RT_)                                                                                                                  \
-    hipLaunchKernelGGL((k_sparse_conv_mfma_f16x_c16<CO, RT_>), dim3((unsigned)st_div_up(n_out, (MF_BLOCK / 64) * 16 * RT_)), dim3(MF_BLOCK), 0, \
-                       stream, (const st_h*)x0, nbr, K, n_out, nstride, (const st_v8h*)w, scale, shift, (const st_h*)residual, relu, (st_h*)y, row_order)
-            if (cout == 16) { if (rt16 == 2) F16C_LAUNCH(16, 2); else F16C_LAUNCH(16, 1); }
-            else { if (rt16 == 2) F16C_LAUNCH(32, 2); else F16C_LAUNCH(32, 1); }
-#undef F16C_LAUNCH
-            ST_CHECK_LAUNCH();
-            return ST_OK;
-        }
-        if (cin % 32 == 0) {  // 32-deep instruction; weights in the 32-channel operand order (mfma_weight32)
-            const int rt = n_out >= (row_order == nullptr ? 56000 : 300000) ? 2 : 1;
-#define F16X_LAUNCH(CI, CO, RT_)                                                                                                          \
-    hipLaunchKernelGGL((k_sparse_conv_mfma_f16x<CI, CO, RT_>), dim3((unsigned)st_div_up(n_out, (MF_BLOCK / 64) * 16 * RT_)), dim3(MF_BLOCK), 0, \
-                       stream, (const st_h*)x0, c0, (const st_h*)x1, nbr, K, n_out, nstride, (const st_v8h*)w, scale, shift,               \
-                       (const st_h*)residual, relu, (st_h*)y, row_order)
-#define F16X_CASE(CI, CO)                                                    \
-    if (cin == CI && cout == CO) {                                           \
-        if (rt == 2) F16X_LAUNCH(CI, CO, 2); else F16X_LAUNCH(CI, CO, 1);    \
-        ST_CHECK_LAUNCH();                                                   \
-        return ST_OK;                                                        \
-    }
-            F16X_CASE(32, 16)
-            F16X_CASE(32, 32)
-            F16X_CASE(32, 64)
-            F16X_CASE(64, 32)
-            F16X_CASE(64, 64)
+        const int rt = conv_row_tiles(a);
+#define F16X_CASE(CI, CO) \
+    if (cin == CI && cout == CO) return rt == 2 ? mf_launch(f16x_kernel<CI, CO, 2>(), 2, a) : mf_launch(f16x_kernel<CI, CO, 1>(), 1, a);
+        F16X_CASE(16, 16)
+        F16X_CASE(16, 32)
+        F16X_CASE(32, 16)
+        F16X_CASE(32, 32)
+        F16X_CASE(32, 64)
+        F16X_CASE(64, 32)
+        F16X_CASE(64, 64)
 #undef F16X_CASE
-#undef F16X_LAUNCH
-        }
         st_set_error("conv(f16): no kernel instance for cin=%d cout=%d", cin, cout);
         return ST_ERR_INVALID;
     }
     ST_REQUIRE(residual == nullptr && c0 == cin, "conv(f16): the converting kernels take no residual and no concat");
     ST_REQUIRE(cin % 4 == 0 && cout % 4 == 0, "conv(f16): channels must be multiples of 4");
-#define CAST_CASE(CI, CO, COT_)                                                                                                 \
-    if (cin == CI && cout == CO) {                                                                                              \
-        if (in_half) return conv_launch<CI, COT_, st_h, float>((const st_h*)x0, c0, (const st_h*)x1, nbr, K, n_out, nstride, (const float*)w, \
-                                                               cout, scale, shift, nullptr, relu, (float*)y, stream, row_order); \
-        return conv_launch<CI, COT_, float, st_h>((const float*)x0, c0, (const float*)x1, nbr, K, n_out, nstride, (const float*)w, cout,   \
-                                                  scale, shift, nullptr, relu, (st_h*)y, stream, row_order);                     \
-    }
+#define CAST_CASE(CI, CO, COT_) \
+    if (cin == CI && cout == CO) return in_half ? conv_launch<CI, COT_, st_h, float>(a, cout) : conv_launch<CI, COT_, float, st_h>(a, cout);
     CAST_CASE(8, 16, 16)
     CAST_CASE(16, 8, 8)
     CAST_CASE(16, 32, 16)
@@ -822,15 +564,12 @@ extern "C" int st_sparse_conv_mfma_fwd(const float* x0, int c0, const float* x1,
                                        int64_t n_out, const float* wp, int cout, const float* scale, const float* shift,
                                        const float* residual, int relu, float* y, const int32_t* row_order, void* stream_,
                                        int64_t nbr_stride, int variant) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t nstride = nbr_stride > 0 ? nbr_stride : n_out;
-    ST_REQUIRE(K >= 1 && (nbr != nullptr || K == 1), "conv: a NULL neighbour table means pointwise (K = 1)");
-    ST_REQUIRE(c0 > 0 && c0 <= cin && (c0 == cin || x1 != nullptr), "conv: bad concat split");
-    ST_REQUIRE((scale == nullptr) == (shift == nullptr), "conv: scale and shift go together");
+    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, wp, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_};
+    ST_TRY(conv_check_args(&a, cin));
     ST_REQUIRE(cin % 16 == 0 && cout % 16 == 0 && c0 % 16 == 0, "conv(mfma): channels and concat split must be multiples of 16");
     if (n_out <= 0) return ST_OK;
 #define MFMA_CASE(CI, CO) \
-    if (cin == CI && cout == CO) return conv_launch_mfma<CI, CO>(x0, c0, x1, nbr, K, n_out, nstride, wp, scale, shift, residual, relu, y, stream, row_order, variant);
+    if (cin == CI && cout == CO) return conv_launch_mfma<CI, CO>(a, variant);
     MFMA_CASE(16, 16)
     MFMA_CASE(16, 32)
     MFMA_CASE(32, 16)
@@ -856,19 +595,15 @@ extern "C" int st_sparse_conv_fwd(const float* x0, int c0, const float* x1, int 
                                   int64_t n_out, const float* w, int cout, const float* scale, const float* shift,
                                   const float* residual, int relu, float* y, const int32_t* row_order, void* stream_,
                                   int64_t nbr_stride) {
-    hipStream_t stream = (hipStream_t)stream_;
-    const int64_t nstride = nbr_stride > 0 ? nbr_stride : n_out;
-    ST_REQUIRE(K >= 1 && (nbr != nullptr || K == 1), "conv: a NULL neighbour table means pointwise (K = 1)");
-    ST_REQUIRE(c0 > 0 && c0 <= cin && (c0 == cin || x1 != nullptr), "conv: bad concat split");
-    ST_REQUIRE((scale == nullptr) == (shift == nullptr), "conv: scale and shift go together");
+    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, w, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_};
+    ST_TRY(conv_check_args(&a, cin));
     ST_REQUIRE(cout >= 1, "conv: cout must be positive");
     if (n_out <= 0) return ST_OK;
     // the instantiated kernels read the concatenated row in float4 pieces: they take a split on a multiple of 4 channels (or no
     // concat when Cin % 4 != 0); any other split 0 < c0 <= cin goes to the generic kernel below -- the same order of operations,
     // so the same bits the instance would give
-#define CONV_CASE(CI, CO, COT_)                                                                                  \
-    if (cin == CI && cout == CO && (c0 == cin || (CI % 4 == 0 && c0 % 4 == 0)))                                  \
-        return conv_launch<CI, COT_>(x0, c0, x1, nbr, K, n_out, nstride, w, cout, scale, shift, residual, relu, y, stream, row_order);
+#define CONV_CASE(CI, CO, COT_) \
+    if (cin == CI && cout == CO && (c0 == cin || (CI % 4 == 0 && c0 % 4 == 0))) return conv_launch<CI, COT_>(a, cout);
     CONV_CASE(3, 8, 8)
     CONV_CASE(8, 8, 8)
     CONV_CASE(8, 16, 16)
@@ -883,8 +618,8 @@ extern "C" int st_sparse_conv_fwd(const float* x0, int c0, const float* x1, int 
 #undef CONV_CASE
     // any other channel counts (a model config away from the shipped planes, e.g. colour as input channels 4-6) or concat split:
     // the generic kernel
-    hipLaunchKernelGGL(k_sparse_conv_any, dim3((unsigned)st_div_up(n_out, CONV_BLOCK), (unsigned)st_div_up(cout, 4)), dim3(CONV_BLOCK), 0, stream, x0, c0,
-                       x1, cin, nbr, K, n_out, nstride, w, cout, scale, shift, residual, relu, y, row_order);
+    hipLaunchKernelGGL(k_sparse_conv_any, dim3((unsigned)st_div_up(n_out, CONV_BLOCK), (unsigned)st_div_up(cout, 4)), dim3(CONV_BLOCK), 0, a.stream, x0, c0,
+                       x1, cin, nbr, K, n_out, a.nstride, w, cout, scale, shift, residual, relu, y, row_order);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }

@@ -338,58 +338,36 @@ def sparse_conv(x0: torch.Tensor, w: torch.Tensor, nbr: Optional[torch.Tensor], 
     if n_out == 0:  # an empty active set (a cloud without a block of > 20 points): nothing to launch
         return torch.empty((0, cout), dtype=torch.float16 if out_half else torch.float32, device=x0.device)
     in_half = x0.dtype == torch.float16
-    if in_half or out_half:
-        both = in_half and out_half
-        if both and wp16 is None:
-            raise ValueError("half -> half convolution needs the half-precision MFMA weights (wp16)")
-        y = torch.empty((n_out, cout), dtype=torch.float16 if out_half else torch.float32, device=x0.device)
-        esz_in, esz_out = (2 if in_half else 4), (2 if out_half else 4)
-        nbytes = (lambda: (_pair_count(nbr) if nbr is not None else n_out) * (cin * esz_in + (4 if nbr is not None else 0))
-                  + n_out * cout * esz_out) if profiling.enabled() else 0
-        nflops = (lambda: 2.0 * (_pair_count(nbr) if nbr is not None else n_out) * cin * cout) if profiling.enabled() else 0
-        name = f"k_sparse_conv_mfma_f16x<{cin},{cout}>" if both else f"k_sparse_conv<{cin},{cout}> {'h->f' if in_half else 'f->h'}"
-        with profiling.kernel(name + ("" if nbr is not None else " k1"), nbytes, nflops):
-            _lib.check(L.st_sparse_conv_f16_fwd(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out,
-                                                _lib.ptr(wp16 if both else w), cout, _lib.ptr(scale), _lib.ptr(shift),
-                                                _lib.ptr(residual), int(relu), _lib.ptr(y), int(in_half), int(out_half),
-                                                _lib.ptr(row_order), _lib.stream(x0.device), nbr_stride))
-        return y
     # 16 -> 16 submanifold convs run on the vector kernel (lane = voxel, weights from scalar registers): with Morton-ordered
     # rows it beats the matrix-core kernel wherever the level fills the chip (67 % against 53 % of the HBM peak at 1.5M rows,
     # profiles/r02_conv_layers_batch16.txt).  At EVERY size, not only the large ones: the two kernels round differently in
     # the last bit (the matrix core does not evaluate a k-ordered fmaf chain exactly), and a cloud must get the same values
     # alone and inside a batch (tests/test_batch.py).
-    if wq is not None and b3_eligible(cin, cout, c0):
-        y = torch.empty((n_out, cout), dtype=torch.float32, device=x0.device)
-        nbytes = (lambda: (_pair_count(nbr) if nbr is not None else n_out) * (cin * 4 + (4 if nbr is not None else 0))
-                  + n_out * cout * 4) if profiling.enabled() else 0
-        nflops = (lambda: 2.0 * (_pair_count(nbr) if nbr is not None else n_out) * cin * cout) if profiling.enabled() else 0
-        with profiling.kernel(f"k_sparse_conv_mfma_b3<{cin},{cout}>" + ("" if nbr is not None else " k1"), nbytes, nflops):
-            _lib.check(L.st_sparse_conv_b3_fwd(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, _lib.ptr(wq), cout,
-                                               _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), int(relu), _lib.ptr(y),
-                                               _lib.ptr(row_order), _lib.stream(x0.device), nbr_stride, int(B3_VARIANT)))
-        return y
     big_16 = cin == 16 and cout == 16 and nbr is not None and row_order is None and x1 is None
-    if wp is not None and mfma_eligible(cin, cout, c0) and not big_16:
-        y = torch.empty((n_out, cout), dtype=torch.float32, device=x0.device)
-        nbytes = (lambda: (_pair_count(nbr) if nbr is not None else n_out) * (cin * 4 + (4 if nbr is not None else 0))
-                  + n_out * cout * 4) if profiling.enabled() else 0
-        nflops = (lambda: 2.0 * (_pair_count(nbr) if nbr is not None else n_out) * cin * cout) if profiling.enabled() else 0
-        with profiling.kernel(f"k_sparse_conv_mfma<{cin},{cout}>" + ("" if nbr is not None else " k1"), nbytes, nflops):
-            _lib.check(L.st_sparse_conv_mfma_fwd(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, _lib.ptr(wp), cout,
-                                                 _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), int(relu), _lib.ptr(y),
-                                                 _lib.ptr(row_order), _lib.stream(x0.device), nbr_stride, int(MFMA_VARIANT)))
-        return y
-    y = torch.empty((n_out, cout), dtype=torch.float32, device=x0.device)
-    # algorithmic bytes: P*(Cin*4 + 4) + N*Cout*4 (pointwise: N*(Cin+Cout)*4); the pair count
-    # is evaluated lazily, after the timed region
-    nbytes = (lambda: (_pair_count(nbr) if nbr is not None else n_out) * (cin * 4 + (4 if nbr is not None else 0))
-              + n_out * cout * 4) if profiling.enabled() else 0
+    # per branch: entry point, its weights, profiling name, arguments between y and row_order, arguments after nbr_stride
+    mid, tail = (), ()
+    if in_half or out_half:
+        both = in_half and out_half
+        if both and wp16 is None:
+            raise ValueError("half -> half convolution needs the half-precision MFMA weights (wp16)")
+        entry, wt, mid = L.st_sparse_conv_f16_fwd, (wp16 if both else w), (int(in_half), int(out_half))
+        name = f"k_sparse_conv_mfma_f16x<{cin},{cout}>" if both else f"k_sparse_conv<{cin},{cout}> {'h->f' if in_half else 'f->h'}"
+    elif wq is not None and b3_eligible(cin, cout, c0):
+        entry, wt, name, tail = L.st_sparse_conv_b3_fwd, wq, f"k_sparse_conv_mfma_b3<{cin},{cout}>", (int(B3_VARIANT),)
+    elif wp is not None and mfma_eligible(cin, cout, c0) and not big_16:
+        entry, wt, name, tail = L.st_sparse_conv_mfma_fwd, wp, f"k_sparse_conv_mfma<{cin},{cout}>", (int(MFMA_VARIANT),)
+    else:
+        entry, wt, name = L.st_sparse_conv_fwd, w, f"k_sparse_conv<{cin},{cout}>"
+    esz_in, esz_out = (2 if in_half else 4), (2 if out_half else 4)
+    y = torch.empty((n_out, cout), dtype=torch.float16 if out_half else torch.float32, device=x0.device)
+    # algorithmic bytes: P*(Cin*4 + 4) + N*Cout*4 (pointwise: N*(Cin+Cout)*4; 2-byte elements on a half side); the
+    # pair count is evaluated lazily, after the timed region
+    nbytes = (lambda: (_pair_count(nbr) if nbr is not None else n_out) * (cin * esz_in + (4 if nbr is not None else 0))
+              + n_out * cout * esz_out) if profiling.enabled() else 0
     nflops = (lambda: 2.0 * (_pair_count(nbr) if nbr is not None else n_out) * cin * cout) if profiling.enabled() else 0
-    with profiling.kernel(f"k_sparse_conv<{cin},{cout}>" + ("" if nbr is not None else " k1"), nbytes, nflops):
-      _lib.check(L.st_sparse_conv_fwd(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, _lib.ptr(w), cout,
-                                    _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), int(relu), _lib.ptr(y),
-                                    _lib.ptr(row_order), _lib.stream(x0.device), nbr_stride))
+    with profiling.kernel(name + ("" if nbr is not None else " k1"), nbytes, nflops):
+        _lib.check(entry(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, _lib.ptr(wt), cout, _lib.ptr(scale), _lib.ptr(shift),
+                         _lib.ptr(residual), int(relu), _lib.ptr(y), *mid, _lib.ptr(row_order), _lib.stream(x0.device), nbr_stride, *tail))
     return y
 
 

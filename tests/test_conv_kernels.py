@@ -520,12 +520,16 @@ def test_sparse_ops_routes_the_shipped_layers(backend, monkeypatch):
 
 # ------------------------------------------------------------------------------------------------------------ coverage ---
 def dispatched_instances(src: str):
-    """(macro, shape) of every kernel instance the dispatch code of sparse_conv.hip names (numeric macro arguments only: the
-    #define lines take parameter names)."""
+    """(table, shape) of every kernel instance the dispatch tables of sparse_conv.hip name: their rows are <TABLE>_CASE(cin, cout[,
+    cout tile]) (numeric macro arguments only: the #define lines take parameter names).  A sixteen-input-channel row of the
+    split-bf16 / half tables is the pair kernel, counted per row-tile count: ("B3_C16" / "F16X_C16", (cout, row tiles))."""
     out = set()
-    for macro in ("CONV_CASE", "MFMA_CASE", "B3_CASE", "B3_LAUNCH16", "F16C_LAUNCH", "F16X_CASE", "CAST_CASE"):
-        for m in re.finditer(rf"\b{macro}\((\d+),\s*(\d+)(?:,\s*(\d+))?\)", src):
-            out.add((macro, tuple(int(g) for g in m.groups() if g is not None)))
+    for m in re.finditer(r"\b([A-Z0-9]+)_CASE\((\d+),\s*(\d+)(?:,\s*(\d+))?\)", src):
+        table, args = m.group(1), tuple(int(g) for g in m.groups()[1:] if g is not None)
+        if table in ("B3", "F16X") and args[0] == 16:
+            out |= {(table + "_C16", (args[1], rt)) for rt in (1, 2)}
+        else:
+            out.add((table, args))
     return out
 
 
@@ -533,13 +537,13 @@ def uncovered(src: str):
     cov = {(c.family, c.cin, c.cout, c.variant) for c in CASES}
     cov |= {(c.family, c.cin, c.cout, 2) for c, _, _ in THRESHOLD_CASES} | {(c.family, c.cin, c.cout, 2) for c in RT2_HALF_CASES}
     need = {
-        "CONV_CASE": lambda a: [("vec", a[0], a[1], 0)],
-        "MFMA_CASE": lambda a: [("mfma", a[0], a[1], v) for v in MFMA_VARIANTS],
-        "B3_CASE": lambda a: [("b3", a[0], a[1], rt) for rt in (1, 2)],
-        "B3_LAUNCH16": lambda a: [("b3_c16", 16, a[0], a[1])],
-        "F16C_LAUNCH": lambda a: [("f16x_c16", 16, a[0], 0 if a[1] == 1 else 2)],
-        "F16X_CASE": lambda a: [("f16x", a[0], a[1], 0), ("f16x", a[0], a[1], 2)],
-        "CAST_CASE": lambda a: [("cast_f2h", a[0], a[1], 0), ("cast_h2f", a[0], a[1], 0)],
+        "CONV": lambda a: [("vec", a[0], a[1], 0)],
+        "MFMA": lambda a: [("mfma", a[0], a[1], v) for v in MFMA_VARIANTS],
+        "B3": lambda a: [("b3", a[0], a[1], rt) for rt in (1, 2)],
+        "B3_C16": lambda a: [("b3_c16", 16, a[0], a[1])],
+        "F16X_C16": lambda a: [("f16x_c16", 16, a[0], 0 if a[1] == 1 else 2)],
+        "F16X": lambda a: [("f16x", a[0], a[1], 0), ("f16x", a[0], a[1], 2)],
+        "CAST": lambda a: [("cast_f2h", a[0], a[1], 0), ("cast_h2f", a[0], a[1], 0)],
     }
     return sorted((macro, args) for macro, args in dispatched_instances(src) if not set(need[macro](args)) <= cov)
 
@@ -552,7 +556,9 @@ def test_every_dispatched_instance_has_a_case():
     assert uncovered(src) == []
     # the check notices a new instance
     extra = src.replace("    CONV_CASE(3, 8, 8)\n", "    CONV_CASE(3, 8, 8)\n    CONV_CASE(12, 24, 8)\n")
-    assert extra != src and uncovered(extra) == [("CONV_CASE", (12, 24, 8))]
+    assert extra != src and uncovered(extra) == [("CONV", (12, 24, 8))]
+    extra = src.replace("    B3_CASE(16, 32)\n", "    B3_CASE(16, 32)\n    B3_CASE(16, 64)\n")  # a pair-kernel row: both row-tile counts
+    assert extra != src and uncovered(extra) == [("B3_C16", (64, 1)), ("B3_C16", (64, 2))]
 
 
 def test_half_weights_only_for_shapes_with_a_kernel():

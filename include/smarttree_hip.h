@@ -27,7 +27,9 @@ extern "C" {
 #endif
 
 /* 101 (round 6): st_abi_entries added; stats_host of the skeleton calls is 16 x int64 (8 before 100) and their tuning array
- * 24 x int64 -- a caller built against an older header must check st_abi_entries before passing shorter arrays. */
+ * 24 x int64 -- a caller built against an older header must check st_abi_entries before passing shorter arrays.
+ * 105: st_centre_cloud_box_seg and st_voxelize_blocks_box_seg added (no existing signature or st_abi_entries value changed);
+ * st_component_csr_knn_workspace_bytes asks for one more int32 per table entry. */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -229,6 +231,18 @@ int st_points_to_nearest_tube(const float* pts, int64_t n, const float* a, const
  *           clouds never share a neighbourhood, a grid slab, a spatial extent or a component. */
 int st_centre_cloud_seg(const float* xyz, int64_t n, const int32_t* seg_off, int nseg, float* out, void* ws,
                         int64_t ws_bytes /* >= 24 * nseg + 256 */, void* stream);
+/* st_centre_cloud_box_seg = st_centre_cloud_seg that also leaves, per cloud, the bounding box of the CENTRED points in box_out
+ * (device, [nseg][6] float: min xyz, max xyz; min = +inf, max = -inf for an empty cloud).  st_voxelize_blocks_box_seg =
+ * st_voxelize_blocks_seg that takes that box (centred_box, NULL = none) instead of reducing it from the points once more: valid
+ * only for the very array the centring call wrote (same points, same seg_off).  Results are identical with and without it. */
+int st_centre_cloud_box_seg(const float* xyz, int64_t n, const int32_t* seg_off, int nseg, float* out, void* ws,
+                            int64_t ws_bytes /* >= 24 * nseg + 256 */, void* stream, float* box_out);
+int st_voxelize_blocks_box_seg(const float* xyz, const float* rgb, int64_t n, const int32_t* seg_off, int nseg,
+                               double voxel_size, double block_size, double buffer_size, int min_points, int max_blocks,
+                               int64_t max_voxels, float* feats, int32_t* coords, uint8_t* mask, int64_t* point_index,
+                               float* block_centres, int32_t* blk_seg, int32_t* seg_vox_off, int32_t* seg_blk_off,
+                               int64_t* n_voxels_host, int64_t* n_blocks_host, void* ws, int64_t ws_bytes, void* stream,
+                               const float* centred_box /*[nseg][6] or NULL*/);
 int64_t st_voxelize_workspace_bytes_seg(int64_t n_points, int max_blocks, int64_t max_voxels, int nseg);
 int st_voxelize_blocks_seg(const float* xyz, const float* rgb, int64_t n, const int32_t* seg_off, int nseg,
                            double voxel_size, double block_size, double buffer_size, int min_points, int max_blocks,

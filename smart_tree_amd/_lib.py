@@ -72,6 +72,9 @@ SIGNATURES = {
     "st_skeleton_workspace_bytes": (I64, [I64, I64]),
     # batched forms (B clouds per launch set)
     "st_centre_cloud_seg": (c_int, [P, I64, P, c_int, P, P, I64, P]),
+    "st_centre_cloud_box_seg": (c_int, [P, I64, P, c_int, P, P, I64, P, P]),
+    "st_voxelize_blocks_box_seg": (c_int, [P, P, I64, P, c_int, c_double, c_double, c_double, c_int, c_int, I64, P, P, P, P, P, P, P, P,
+                                           ctypes.POINTER(I64), ctypes.POINTER(I64), P, I64, P, P]),
     "st_voxelize_workspace_bytes_seg": (I64, [I64, c_int, I64, c_int]),
     "st_voxelize_blocks_seg": (c_int, [P, P, I64, P, c_int, c_double, c_double, c_double, c_int, c_int, I64, P, P, P, P, P, P, P, P,
                                        ctypes.POINTER(I64), ctypes.POINTER(I64), P, I64, P]),
@@ -124,7 +127,7 @@ ENQUEUE_ONLY = frozenset({
     "st_build_coord_hash", "st_build_subm_rulebook", "st_build_strided_rulebook", "st_sparse_conv_fwd",
     "st_sparse_conv_mfma_fwd", "st_sparse_conv_b3_fwd", "st_sparse_conv_f16_fwd", "st_pointwise_mlp_heads", "st_medial_points", "st_centre_cloud",
     "st_connected_components", "st_component_csr", "st_post_process", "st_knn_radius", "st_brick_pyramid_workspace_bytes",
-    "st_centre_cloud_seg", "st_voxelize_workspace_bytes_seg", "st_build_strided_rulebook_seg", "st_knn_workspace_bytes_seg",
+    "st_centre_cloud_seg", "st_centre_cloud_box_seg", "st_voxelize_workspace_bytes_seg", "st_build_strided_rulebook_seg", "st_knn_workspace_bytes_seg",
     "st_knn_radius_seg", "st_skeleton_workspace_bytes_seg", "st_post_process_seg", "st_radius_count_seg",
     "st_voxelize_cloud_workspace_bytes", "st_loss_workspace_bytes", "st_spatial_order_workspace_bytes", "st_spatial_order", "st_connected_components_knn", "st_component_csr_knn", "st_component_csr_knn_workspace_bytes", "st_move_rows",
     "st_loss_backward", "st_sparse_conv_wgrad_workspace_bytes", "st_sparse_conv_wgrad",

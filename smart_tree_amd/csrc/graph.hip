@@ -108,7 +108,10 @@ __global__ void __launch_bounds__(GR_BLOCK) k_bbox(const float* xyz, int64_t n, 
     __syncthreads();
     if (threadIdx.x < 3 && r.i1 > r.i0) { atomicMin(&box[6 * seg + threadIdx.x], lo[threadIdx.x]); atomicMax(&box[6 * seg + 3 + threadIdx.x], hi[threadIdx.x]); }
 }
-__global__ void __launch_bounds__(GR_BLOCK) k_centre(const float* xyz, int64_t n, const unsigned* box, float* out, const int* seg_off) {
+// box_out (optional, [nseg][6]): min xyz, max xyz of the CENTRED cloud -- the two extreme input points moved like every other
+// (x -> fl(x + shift) is monotone, so they stay the extremes); an empty cloud gets min = +inf, max = -inf.
+__global__ void __launch_bounds__(GR_BLOCK) k_centre(const float* xyz, int64_t n, const unsigned* box, float* out, const int* seg_off,
+                                                     float* box_out) {
     const int seg = blockIdx.y;
     const GrRange r = gr_range(xyz, out, n, seg_off, seg);
     float shift[3];
@@ -117,6 +120,10 @@ __global__ void __launch_bounds__(GR_BLOCK) k_centre(const float* xyz, int64_t n
         const float half = (mx - mn) / 2.0f;
         const float centre = mn + half;
         shift[a] = -centre + (a == 1 ? half : 0.0f);
+        if (box_out && blockIdx.x == 0 && threadIdx.x == 0) {
+            box_out[6 * seg + a] = r.i1 > r.i0 ? mn + shift[a] : INFINITY;
+            box_out[6 * seg + 3 + a] = r.i1 > r.i0 ? mx + shift[a] : -INFINITY;
+        }
     }
     const float4* v = reinterpret_cast<const float4*>(xyz + 3 * r.a0);
     float4* o = reinterpret_cast<float4*>(out + 3 * r.a0);
@@ -142,10 +149,15 @@ __global__ void k_box_init(unsigned* box, int nseg) {
 
 // Batched form: `nseg` clouds in one array, cloud b = points [seg_off[b], seg_off[b+1]) (device int32 [nseg+1]); every
 // cloud is centred on ITS OWN bounding box, exactly as the one-cloud call does.  out [n,3]; scratch: 6 x uint32 per cloud.
-extern "C" int st_centre_cloud_seg(const float* xyz, int64_t n, const int32_t* seg_off, int nseg, float* out, void* ws,
-                                   int64_t ws_bytes, void* stream_) {
+// st_centre_cloud_box_seg: the same call, which also leaves the box of every centred cloud in box_out (device, [nseg][6] float)
+// for st_voxelize_blocks_box_seg.
+extern "C" int st_centre_cloud_box_seg(const float* xyz, int64_t n, const int32_t* seg_off, int nseg, float* out, void* ws,
+                                       int64_t ws_bytes, void* stream_, float* box_out) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (n <= 0) return ST_OK;
+    if (n <= 0) {
+        ST_REQUIRE(!box_out, "centre_cloud: no box of an empty array");
+        return ST_OK;
+    }
     ST_REQUIRE(nseg >= 1 && nseg <= ST_MAX_SEG && (nseg == 1 || seg_off), "centre_cloud: 1 <= clouds per batch <= %d", ST_MAX_SEG);
     if (nseg == 1) seg_off = nullptr;
     StArena a(ws, ws_bytes);
@@ -158,9 +170,13 @@ extern "C" int st_centre_cloud_seg(const float* xyz, int64_t n, const int32_t* s
     const unsigned gx = (unsigned)st_min64(st_div_up(per > 0 ? per : 1, GR_BLOCK), 2048 / (nseg < 8 ? nseg : 8) + 1);
     hipLaunchKernelGGL(k_bbox, dim3(gx, (unsigned)nseg), dim3(GR_BLOCK), 0, stream, xyz, n, box, seg_off);
     hipLaunchKernelGGL(k_centre, dim3((unsigned)st_min64(st_div_up(per > 0 ? per : 1, GR_BLOCK), 8192), (unsigned)nseg), dim3(GR_BLOCK), 0, stream,
-                       xyz, n, (const unsigned*)box, out, seg_off);
+                       xyz, n, (const unsigned*)box, out, seg_off, box_out);
     ST_CHECK_LAUNCH();
     return ST_OK;
+}
+extern "C" int st_centre_cloud_seg(const float* xyz, int64_t n, const int32_t* seg_off, int nseg, float* out, void* ws,
+                                   int64_t ws_bytes, void* stream_) {
+    return st_centre_cloud_box_seg(xyz, n, seg_off, nseg, out, ws, ws_bytes, stream_, nullptr);
 }
 extern "C" int st_centre_cloud(const float* xyz, int64_t n, float* out, void* ws, int64_t ws_bytes, void* stream_) {
     return st_centre_cloud_seg(xyz, n, nullptr, 1, out, ws, ws_bytes, stream_);
@@ -638,10 +654,18 @@ __global__ void __launch_bounds__(GR_BLOCK) k_csr_fill(GrEdges G, int64_t E, con
 // distance do not change, the SSSP relaxes ~40 % fewer entries.
 #define CSRK_MUTUAL 0x40000000
 struct __attribute__((aligned(16))) GrI64x2 { int64_t x, y; };  // one 16-byte load of two table entries
-template <int K>
-__global__ void __launch_bounds__(GR_BLOCK) k_csrk_count(const int64_t* __restrict__ idx, int64_t n, const int* __restrict__ first_of,
-                                                         const int* __restrict__ new_id, uint32_t* deg, uint32_t* fwdc,
-                                                         int32_t* __restrict__ tgt) {
+struct __attribute__((aligned(16))) GrI32x4 { int32_t x, y, z, w; };  // one 16-byte load of four packed entries
+// The mutual test reads a whole row of the OTHER endpoint per edge: with the table's int64 entries that is 8K bytes (K = 16: a
+// 128-byte line, ~19x the table in traffic).  idx32 (PACKED) is the same table narrowed to int32 by one streaming pass
+// (k_csrk_pack: entries are -1 or a vertex < n < 2^31): a row is 4K bytes -- K = 16: four 16-byte loads inside ONE 64-byte
+// sector -- and the pass reads its own entries from it too, so the int64 table is streamed once instead of gathered.
+__global__ void __launch_bounds__(GR_BLOCK) k_csrk_pack(const int64_t* __restrict__ idx, int64_t E, int32_t* __restrict__ idx32) {
+    GR_LOOP(e, E) idx32[e] = (int32_t)idx[e];
+}
+template <int K, bool PACKED>
+__global__ void __launch_bounds__(GR_BLOCK) k_csrk_count(const int64_t* __restrict__ idx, const int32_t* __restrict__ idx32, int64_t n,
+                                                         const int* __restrict__ first_of, const int* __restrict__ new_id, uint32_t* deg,
+                                                         uint32_t* fwdc, int32_t* __restrict__ tgt) {
     const int64_t E = n * K;
     const int lane = threadIdx.x & 63;
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < E; base += (int64_t)gridDim.x * blockDim.x) {
@@ -651,12 +675,22 @@ __global__ void __launch_bounds__(GR_BLOCK) k_csrk_count(const int64_t* __restri
         bool mutual = false;
         if (e < E) {
             x = new_id[i];  // (the K lanes of a source read one word)
-            const int64_t j = idx[e], first = first_of ? first_of[i] : 0;
+            const int64_t j = PACKED ? (int64_t)idx32[e] : idx[e], first = first_of ? first_of[i] : 0;
             if (x >= 0 && j > first && j != i) {
                 y = new_id[j];
                 if (y >= 0 && i > first) {  // does j list i?  (that entry is valid by the same rule: i > first, i != j, both kept)
                     const int64_t* row = idx + j * K;
-                    if (K % 2 == 0) {
+                    if (PACKED && K % 4 == 0) {
+                        const int32_t* row32 = idx32 + j * K;
+                        const int32_t i32 = (int32_t)i;
+#pragma unroll
+                        for (int k = 0; k < K; k += 4) {
+                            const GrI32x4 r = *reinterpret_cast<const GrI32x4*>(row32 + k);
+                            mutual = mutual || r.x == i32 || r.y == i32 || r.z == i32 || r.w == i32;
+                        }
+                    } else if (PACKED) {
+                        for (int k = 0; k < K; k++) mutual = mutual || (int64_t)idx32[j * K + k] == i;
+                    } else if (K % 2 == 0) {
 #pragma unroll
                         for (int k = 0; k < K; k += 2) {
                             const GrI64x2 r = *reinterpret_cast<const GrI64x2*>(row + k);
@@ -721,6 +755,7 @@ extern "C" int64_t st_component_csr_knn_workspace_bytes(int64_t m, int64_t n, in
     a.take<char>(st_scan_ws_bytes(m + 1));
     a.take<uint32_t>(m + 1);
     a.take<int32_t>(n * (int64_t)(K > 0 ? K : 1));
+    a.take<int32_t>(n * (int64_t)(K > 0 ? K : 1));  // the int32 copy of the table (k_csrk_pack)
     return a.used;
 }
 
@@ -741,11 +776,18 @@ extern "C" int st_component_csr(const int64_t* edges, const float* w, int64_t E,
 // (or a K that is not a power of two <= 64) the call falls back to the edge-list build, which keeps both copies of a mutual pair.
 template <int K>
 static void csrk_launch(const int64_t* idx, const float* dist, int64_t n, const int32_t* first_of, const int32_t* new_id, int64_t m,
-                        uint32_t* row_off, uint32_t* col, float* wgt, uint32_t* cursor, uint32_t* fwdc, int32_t* tgt, char* sw, int64_t sb,
-                        hipStream_t stream, int* rc) {
+                        uint32_t* row_off, uint32_t* col, float* wgt, uint32_t* cursor, uint32_t* fwdc, int32_t* tgt, int32_t* idx32,
+                        char* sw, int64_t sb, hipStream_t stream, int* rc) {
     const int64_t E = n * K;
     (void)hipMemsetAsync(row_off, 0, (m + 1) * sizeof(uint32_t), stream);
-    hipLaunchKernelGGL((k_csrk_count<K>), dim3(gr_grid(E)), dim3(GR_BLOCK), 0, stream, idx, n, first_of, new_id, row_off, fwdc, tgt);
+    if (idx32) {
+        hipLaunchKernelGGL(k_csrk_pack, dim3(gr_grid(E)), dim3(GR_BLOCK), 0, stream, idx, E, idx32);
+        hipLaunchKernelGGL((k_csrk_count<K, true>), dim3(gr_grid(E)), dim3(GR_BLOCK), 0, stream, idx, (const int32_t*)idx32, n, first_of,
+                           new_id, row_off, fwdc, tgt);
+    } else {
+        hipLaunchKernelGGL((k_csrk_count<K, false>), dim3(gr_grid(E)), dim3(GR_BLOCK), 0, stream, idx, (const int32_t*)nullptr, n, first_of,
+                           new_id, row_off, fwdc, tgt);
+    }
     *rc = st_exclusive_scan_u32(row_off, row_off, m + 1, nullptr, sw, sb, stream);
     if (*rc != ST_OK) return;
     hipLaunchKernelGGL(k_csrk_cursor, dim3(gr_grid(m)), dim3(GR_BLOCK), 0, stream, (const uint32_t*)row_off, (const uint32_t*)fwdc, m, cursor);
@@ -765,9 +807,11 @@ extern "C" int st_component_csr_knn(const int64_t* idx, const float* dist, int64
         char* sw = a.take<char>(sb);
         uint32_t* fwdc = a.take<uint32_t>(m + 1);
         int32_t* tgt = a.take<int32_t>(n * (int64_t)K);
-        if (!cursor || !sw || !fwdc || !tgt) { st_set_error("component_csr(knn): workspace too small"); return ST_ERR_WORKSPACE; }
+        int32_t* idx32 = a.take<int32_t>(n * (int64_t)K);
+        if (!cursor || !sw || !fwdc || !tgt || !idx32) { st_set_error("component_csr(knn): workspace too small"); return ST_ERR_WORKSPACE; }
+        if (n >= (1ll << 31)) idx32 = nullptr;  // a vertex id would not fit: the rows are read as they are
         int rc = ST_OK;
-#define CSRK_CASE(K_) case K_: csrk_launch<K_>(idx, dist, n, first_of, new_id, m, row_off, col, wgt, cursor, fwdc, tgt, sw, sb, stream, &rc); break;
+#define CSRK_CASE(K_) case K_: csrk_launch<K_>(idx, dist, n, first_of, new_id, m, row_off, col, wgt, cursor, fwdc, tgt, idx32, sw, sb, stream, &rc); break;
         switch (K) { CSRK_CASE(1) CSRK_CASE(2) CSRK_CASE(4) CSRK_CASE(8) CSRK_CASE(16) CSRK_CASE(32) CSRK_CASE(64) }
 #undef CSRK_CASE
         if (rc != ST_OK) return rc;

@@ -80,11 +80,28 @@ __device__ __forceinline__ void vx_stream_points(const float* __restrict__ xyz, 
     }
 }
 
-__global__ void k_vx_init(VxState* st, int table_cells) {
+// box (optional): [nseg][6] = min xyz, max xyz of every cloud AS THE CENTRING CALL WROTE THEM (st_centre_cloud_box_seg: the
+// centred extreme points, min > max for an empty cloud).  vx_block_id is monotone in the coordinate, so the block-id box of a
+// cloud is the block id of those two points -- exactly what k_vx_bbox reduces from the 12 bytes of every point, which is then not
+// launched.  A non-finite coordinate anywhere in a cloud makes its box non-finite (NaN sorts outside the infinities in the
+// centring call's order-preserving reduction and poisons the shift): same flag as k_vx_bbox raises.
+__global__ void k_vx_init(VxState* st, int table_cells, const float* box, VxParams p) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         st->table_cells = table_cells;
         for (int a = 0; a < 3; a++) { st->lo[a] = 0x7fffffff; st->hi[a] = (int)0x80000000; }
         st->n_blocks = 0; st->n_vox = 0; st->overflow = 0;
+        for (int s = 0; box && s < p.nseg; s++) {
+            const float* b = box + 6 * s;
+            if (b[0] > b[3]) continue;  // empty cloud
+            bool finite = true;
+            for (int j = 0; j < 6; j++) finite = finite && fabsf(b[j]) <= 3.0e38f;
+            if (!finite) { st->overflow |= 16u; continue; }
+            for (int a = 0; a < 3; a++) {
+                const int l = vx_block_id(b[a], p), h = vx_block_id(b[3 + a], p);
+                st->lo[a] = l < st->lo[a] ? l : st->lo[a];
+                st->hi[a] = h > st->hi[a] ? h : st->hi[a];
+            }
+        }
     }
 }
 
@@ -147,7 +164,7 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vx_hist(const float* xyz, int64_t 
 
 // single workgroup: counts -> block rank (or -1), centres, bbox init; cells are walked cloud by cloud
 __global__ void __launch_bounds__(VX_BLOCK) k_vx_blocks(VxState* st, int* table, VxParams p, float* centres, unsigned* blk_lo,
-                                                        unsigned* blk_hi, int32_t* blk_seg) {
+                                                        unsigned* blk_hi, int32_t* blk_seg, int* blk_cell) {
     __shared__ uint32_t lds[VX_BLOCK / 64 + 1];
     int d[3];
     if (!vx_dims(st, d)) return;
@@ -172,6 +189,7 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vx_blocks(VxState* st, int* table,
                     blk_hi[3 * rank + a] = 0u;
                 }
                 if (blk_seg) blk_seg[rank] = seg;
+                blk_cell[rank] = (int)g;  // cloud * cells + cell (k_vx_block_grid folds the zone boxes of the cell's surroundings)
             } else {
                 table[g] = -1;
             }
@@ -192,6 +210,20 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vx_blocks(VxState* st, int* table,
 // requested together (eight independent loads), then fn runs for the hits -- eight uniform steps per point.  (Walking the 27
 // combinations and calling fn inside cost a wavefront 27 serialised bodies, each with its own chain of dependent loads: some
 // lane of 64 scattered points sits near every face.)  `table` = the slice of the point's own cloud.
+// One axis of the separable halo test: q = the coordinate's own block column (relative to the table), returns the set of the
+// columns q - 1, q, q + 1 (bits 0, 1, 2) whose halo interval holds the coordinate.
+__device__ __forceinline__ unsigned vx_axis_cols(float v, int lo, int dim, const VxParams& p, int* q) {
+    *q = vx_block_id(v, p) - lo;
+    unsigned ok = 0;
+    for (int o = -1; o <= 1; o++) {
+        const int c = *q + o;
+        if (c < 0 || c >= dim) continue;
+        const float ctr = (float)(c + lo) * p.bs + p.bs_half;
+        if (v >= ctr - p.half_outer && v < ctr + p.half_outer) ok |= 1u << (o + 1);
+    }
+    return ok;
+}
+
 template <class F>
 __device__ __forceinline__ void vx_for_each_block(const float* pt, const VxState* st, const int* d, const int* table,
                                                   const VxParams& p, F fn) {
@@ -201,16 +233,7 @@ __device__ __forceinline__ void vx_for_each_block(const float* pt, const VxState
     }
     int q[3];
     unsigned ok[3];
-    for (int a = 0; a < 3; a++) {
-        q[a] = vx_block_id(pt[a], p) - st->lo[a];
-        ok[a] = 0;
-        for (int o = -1; o <= 1; o++) {
-            const int c = q[a] + o;
-            if (c < 0 || c >= d[a]) continue;
-            const float ctr = (float)(c + st->lo[a]) * p.bs + p.bs_half;
-            if (pt[a] >= ctr - p.half_outer && pt[a] < ctr + p.half_outer) ok[a] |= 1u << (o + 1);
-        }
-    }
+    for (int a = 0; a < 3; a++) ok[a] = vx_axis_cols(pt[a], st->lo[a], d[a], p, &q[a]);
     if (!(ok[0] && ok[1] && ok[2])) return;
     if (__popc(ok[0]) <= 2 && __popc(ok[1]) <= 2 && __popc(ok[2]) <= 2) {
         int lo_opt[3], hi_opt[3];  // column offsets (-1, 0, 1) of the first / second qualifying column, hi = 2: none
@@ -243,14 +266,82 @@ __device__ __forceinline__ void vx_for_each_block(const float* pt, const VxState
     }
 }
 
+// Per-block bounding boxes over the halo members.
+// ZONE regime (blocked mode, a cloud of at most VX_ZONE_MAX zone cells): which halo cubes hold a point is decided per axis by
+// the column set of vx_axis_cols -- one column c, or two neighbours (c, c + 1) where the halos overlap.  Numbering those sets
+// 2c and 2c + 1 cuts every axis into 2 * dim - 1 zones, and ALL points of a zone cell (zx, zy, zz) belong to the same blocks.
+// So a point updates ONE zone cell's box (six words of LDS, read in three 8-byte loads; a write only when it moves a bound)
+// instead of walking up to eight block-table entries and updating eight boxes: the pass was bound by its instruction count
+// (by count of the old body: ~400 vector instructions per point, 8 bodies per point executed by every wavefront whatever its
+// lanes' memberships; 342 -> 114 us per launch set of twenty 1M-point clouds), not by
+// the 12 bytes it reads.  k_vx_block_grid then folds, per block, the <= 27 zone cells around its table cell: the same set of
+// points as before, and minimum / maximum do not depend on the order.  Words are kept as "larger wins" (the low bounds
+// complemented), so an all-zero array is the empty state.  A point whose column set is neither shape (a halo of half a block
+// or more) goes straight to its blocks' boxes with global atomics, as does everything in the other regimes:
+// DIRECT regime: per-block boxes in LDS when the cloud has at most VX_LDS_BLOCKS blocks, else global atomics.
+#define VX_ZONE_MAX 1024
+__device__ __forceinline__ bool vx_zone_dims(const int* d, const VxParams& p, int* z) {
+    if (p.whole) return false;
+    int64_t total = 1;
+    for (int a = 0; a < 3; a++) { z[a] = 2 * d[a] - 1; total *= z[a]; }
+    return total <= VX_ZONE_MAX;
+}
 __global__ void __launch_bounds__(VX_BLOCK) k_vx_minmax(const float* xyz, int64_t n, const int* seg_off, const VxState* st,
-                                                        const int* table, VxParams p, unsigned* blk_lo, unsigned* blk_hi) {
-    __shared__ unsigned slo[VX_LDS_BLOCKS * 3], shi[VX_LDS_BLOCKS * 3];
-    int d[3];
+                                                        const int* table, VxParams p, unsigned* blk_lo, unsigned* blk_hi,
+                                                        unsigned* zone) {
+    __shared__ __attribute__((aligned(8))) unsigned lds[VX_ZONE_MAX * 6];  // zone regime: boxes of the zone cells; direct: slo | shi
+    int d[3], zd[3];
     if ((st->overflow & 16u) || !vx_dims(st, d)) return;
     const int seg = blockIdx.y;
     const int* tab = table + (int64_t)seg * (d[0] * d[1] * d[2]);
     const int64_t i0 = seg_off ? seg_off[seg] : 0, i1 = seg_off ? seg_off[seg + 1] : n;
+    if (vx_zone_dims(d, p, zd)) {
+        const int ncell = zd[0] * zd[1] * zd[2];
+        for (int i = threadIdx.x; i < ncell * 6; i += blockDim.x) lds[i] = 0u;
+        __syncthreads();
+        const int l0 = st->lo[0], l1 = st->lo[1], l2 = st->lo[2];
+        vx_stream_points(xyz, n, i0, i1, [&](int64_t, float x, float y, float z) {
+            const float pt[3] = {x, y, z};
+            const int lo[3] = {l0, l1, l2};
+            int zc[3];
+            bool plain = true;
+            for (int a = 0; a < 3; a++) {
+                int q;
+                const unsigned ok = vx_axis_cols(pt[a], lo[a], d[a], p, &q);
+                if (ok == 0u) return;  // in no block at all
+                zc[a] = 2 * (q + __ffs(ok) - 2) + (ok == 3u || ok == 6u ? 1 : 0);
+                plain = plain && (ok == 1u || ok == 2u || ok == 4u || ok == 3u || ok == 6u);
+            }
+            const unsigned ox = st_f2ord(x), oy = st_f2ord(y), oz = st_f2ord(z);
+            if (!plain) {
+                vx_for_each_block(pt, st, d, tab, p, [&](int b) {
+                    atomicMin(&blk_lo[3 * b], ox); atomicMin(&blk_lo[3 * b + 1], oy); atomicMin(&blk_lo[3 * b + 2], oz);
+                    atomicMax(&blk_hi[3 * b], ox); atomicMax(&blk_hi[3 * b + 1], oy); atomicMax(&blk_hi[3 * b + 2], oz);
+                });
+                return;
+            }
+            unsigned* cell = &lds[6 * ((zc[0] * zd[1] + zc[1]) * zd[2] + zc[2])];
+            const uint2* c2 = reinterpret_cast<const uint2*>(cell);
+            const uint2 a0 = c2[0], a1 = c2[1], a2 = c2[2];  // ~lo x, ~lo y | ~lo z, hi x | hi y, hi z
+            const unsigned v[6] = {~ox, ~oy, ~oz, ox, oy, oz}, have[6] = {a0.x, a0.y, a1.x, a1.y, a2.x, a2.y};
+            bool moves = false;
+#pragma unroll
+            for (int k = 0; k < 6; k++) moves = moves || v[k] > have[k];
+            if (moves) {
+#pragma unroll
+                for (int k = 0; k < 6; k++)
+                    if (v[k] > have[k]) atomicMax(&cell[k], v[k]);
+            }
+        });
+        __syncthreads();
+        unsigned* out = zone + (int64_t)seg * (VX_ZONE_MAX * 6);
+        for (int i = threadIdx.x; i < ncell * 6; i += blockDim.x) {
+            const unsigned v = lds[i];  // (an earlier workgroup has usually settled the word: look before the atomic)
+            if (v != 0u && v > __hip_atomic_load(&out[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(&out[i], v);
+        }
+        return;
+    }
+    unsigned *slo = lds, *shi = lds + VX_LDS_BLOCKS * 3;
     const int b0 = (int)st->seg_blk_off[seg], nb = (int)st->seg_blk_off[seg + 1] - b0;  // this cloud's blocks
     const bool use_lds = nb <= VX_LDS_BLOCKS;
     if (use_lds)
@@ -280,10 +371,32 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vx_minmax(const float* xyz, int64_
 }
 
 // Per block, once (instead of per point and block): the voxel origin as a float and the grid size roundf((hi - lo) / v).
-__global__ void __launch_bounds__(VX_BLOCK) k_vx_block_grid(VxState* st, int max_blocks, const unsigned* blk_lo,
-                                                            const unsigned* blk_hi, float vs, float* blk_lof, int* blk_grid) {
+// In the zone regime of k_vx_minmax the box of a block is first gathered here: the zones of column c along an axis are 2c - 1
+// (shared with c - 1), 2c and 2c + 1 (shared with c + 1).
+__global__ void __launch_bounds__(VX_BLOCK) k_vx_block_grid(VxState* st, int max_blocks, unsigned* blk_lo, unsigned* blk_hi,
+                                                            VxParams p, float* blk_lof, int* blk_grid, const int* blk_cell,
+                                                            const unsigned* zone) {
+    const float vs = p.vs;
     const int nb = (int)st_min<uint32_t>(st->n_blocks, (uint32_t)max_blocks);
+    int d[3], zd[3];
+    const bool zones = !(st->overflow & 16u) && vx_dims(st, d) && vx_zone_dims(d, p, zd);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 3 * nb; i += gridDim.x * blockDim.x) {
+        if (zones) {
+            const int b = i / 3, a = i % 3, ncell = d[0] * d[1] * d[2];
+            const int g = blk_cell[b], seg = g / ncell, c = g % ncell;
+            const int cc[3] = {c / (d[2] * d[1]), (c / d[2]) % d[1], c % d[2]};
+            const unsigned* zs = zone + (int64_t)seg * (VX_ZONE_MAX * 6);
+            unsigned nlo = ~blk_lo[i], hi = blk_hi[i];
+            for (int zx = st_max(2 * cc[0] - 1, 0); zx <= st_min(2 * cc[0] + 1, zd[0] - 1); zx++)
+                for (int zy = st_max(2 * cc[1] - 1, 0); zy <= st_min(2 * cc[1] + 1, zd[1] - 1); zy++)
+                    for (int zz = st_max(2 * cc[2] - 1, 0); zz <= st_min(2 * cc[2] + 1, zd[2] - 1); zz++) {
+                        const unsigned* cell = zs + 6 * ((zx * zd[1] + zy) * zd[2] + zz);
+                        nlo = st_max(nlo, cell[a]);
+                        hi = st_max(hi, cell[3 + a]);
+                    }
+            blk_lo[i] = ~nlo;
+            blk_hi[i] = hi;
+        }
         const float lo = st_ord2f(blk_lo[i]), hi = st_ord2f(blk_hi[i]);
         blk_lof[i] = lo;
         const float cells = roundf((hi - lo) / vs);
@@ -484,10 +597,15 @@ static inline dim3 vx_grid_seg(int64_t n, int nseg, int64_t cap) {
 static int64_t vx_layout(StArena& a, int64_t n, int max_blocks, int64_t max_voxels, int nseg, VxState** st, int** table,
                          unsigned** blk_lo, unsigned** blk_hi, float** blk_lof, int** blk_grid, VxSlot** slots, uint32_t** cnt, uint32_t** win,
                          uint32_t** rec_b, uint32_t** rec_pt, uint32_t** order, char** sub, int64_t* sub_bytes,
-                         int64_t* cap, float** spare_centres = nullptr, int32_t** spare_i32 = nullptr) {
+                         int64_t* cap, float** spare_centres = nullptr, int32_t** spare_i32 = nullptr, unsigned** zone = nullptr,
+                         int** blk_cell = nullptr) {
     *cap = st_next_pow2((max_voxels > 8 ? max_voxels : 8) + (max_voxels > 8 ? max_voxels : 8) / 2);  // load <= 2/3 at max_voxels
     *st = a.take<VxState>(1);
     *table = a.take<int>(vx_table_cells(max_blocks, nseg) * nseg);
+    unsigned* zn = a.take<unsigned>(6ll * VX_ZONE_MAX * nseg);  // directly behind the table: both are zeroed by one fill
+    int* bc = a.take<int>(max_blocks);
+    if (zone) *zone = zn;
+    if (blk_cell) *blk_cell = bc;
     *blk_lo = a.take<unsigned>(3 * (int64_t)max_blocks);
     *blk_hi = a.take<unsigned>(3 * (int64_t)max_blocks);
     *blk_lof = a.take<float>(3 * (int64_t)max_blocks);
@@ -527,7 +645,7 @@ static int vx_voxelize(const float* xyz, const float* rgb, int64_t n, const int3
                        double block_size, double buffer_size, int min_points, int max_blocks, int64_t max_voxels, float* feats,
                        int32_t* coords, uint8_t* mask, int64_t* point_index, float* block_centres, int32_t* blk_seg,
                        int32_t* seg_vox_off, int32_t* seg_blk_off, int64_t* n_voxels_out, int64_t* n_blocks_out, void* ws,
-                       int64_t ws_bytes, void* stream_, int whole) {
+                       int64_t ws_bytes, void* stream_, int whole, const float* centred_box = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     ST_REQUIRE(n >= 0 && n < (1ll << 31), "voxelize: n_points out of range");
     ST_REQUIRE(voxel_size > 0 && block_size > 0 && buffer_size >= 0 && buffer_size < block_size,
@@ -547,10 +665,10 @@ static int vx_voxelize(const float* xyz, const float* rgb, int64_t n, const int3
     StArena a(ws, ws_bytes);
     VxState* st; int* table; unsigned *blk_lo, *blk_hi; float* blk_lof; int* blk_grid; VxSlot* slots;
     uint32_t *cnt, *win, *rec_b, *rec_pt, *order; char* sub; int64_t sub_bytes, cap;
-    float* spare_centres = nullptr; int32_t* spare_i32 = nullptr;
+    float* spare_centres = nullptr; int32_t* spare_i32 = nullptr; unsigned* zone = nullptr; int* blk_cell = nullptr;
     vx_layout(a, n, max_blocks, max_voxels, nseg, &st, &table, &blk_lo, &blk_hi, &blk_lof, &blk_grid, &slots, &cnt, &win, &rec_b,
-              &rec_pt, &order, &sub, &sub_bytes, &cap, &spare_centres, &spare_i32);
-    if (!a.ok() || !sub || !spare_centres || !spare_i32) {
+              &rec_pt, &order, &sub, &sub_bytes, &cap, &spare_centres, &spare_i32, &zone, &blk_cell);
+    if (!a.ok() || !sub || !spare_centres || !spare_i32 || !zone || !blk_cell) {
         st_set_error("voxelize: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)a.used);
         return ST_ERR_WORKSPACE;
     }
@@ -575,16 +693,18 @@ static int vx_voxelize(const float* xyz, const float* rgb, int64_t n, const int3
     p.nseg = nseg;
 
     const dim3 gr = vx_grid_seg(n, nseg, 512 / (nseg < 8 ? nseg : 8) + 8);
-    hipLaunchKernelGGL(k_vx_init, dim3(1), dim3(64), 0, stream, st, (int)vx_table_cells(max_blocks, nseg));
-    (void)hipMemsetAsync(table, 0, vx_table_cells(max_blocks, nseg) * nseg * sizeof(int), stream);
+    if (whole) centred_box = nullptr;  // (every cloud is block 0: nothing to take over)
+    hipLaunchKernelGGL(k_vx_init, dim3(1), dim3(64), 0, stream, st, (int)vx_table_cells(max_blocks, nseg), centred_box, p);
+    // block table and zone boxes (k_vx_minmax), neighbours in the workspace: one fill
+    (void)hipMemsetAsync(table, 0, (size_t)((char*)(zone + 6ll * VX_ZONE_MAX * nseg) - (char*)table), stream);
     (void)hipMemsetAsync(slots, 0xff, cap * sizeof(VxSlot), stream);  // empty key, value = "no point yet"
-    hipLaunchKernelGGL(k_vx_bbox, gr, dim3(VX_BLOCK), 0, stream, xyz, n, seg_off, p, st);
+    if (!centred_box) hipLaunchKernelGGL(k_vx_bbox, gr, dim3(VX_BLOCK), 0, stream, xyz, n, seg_off, p, st);
     hipLaunchKernelGGL(k_vx_hist, gr, dim3(VX_BLOCK), 0, stream, xyz, n, seg_off, p, st, table);
-    hipLaunchKernelGGL(k_vx_blocks, dim3(1), dim3(VX_BLOCK), 0, stream, st, table, p, block_centres, blk_lo, blk_hi, blk_seg);
+    hipLaunchKernelGGL(k_vx_blocks, dim3(1), dim3(VX_BLOCK), 0, stream, st, table, p, block_centres, blk_lo, blk_hi, blk_seg, blk_cell);
     hipLaunchKernelGGL(k_vx_minmax, gr, dim3(VX_BLOCK), 0, stream, xyz, n, seg_off, (const VxState*)st, (const int*)table, p, blk_lo,
-                       blk_hi);
+                       blk_hi, zone);
     hipLaunchKernelGGL(k_vx_block_grid, dim3((unsigned)st_min64(st_div_up(3 * (int64_t)max_blocks, VX_BLOCK), 64)), dim3(VX_BLOCK), 0, stream,
-                       st, max_blocks, (const unsigned*)blk_lo, (const unsigned*)blk_hi, p.vs, blk_lof, blk_grid);
+                       st, max_blocks, blk_lo, blk_hi, p, blk_lof, blk_grid, (const int*)blk_cell, (const unsigned*)zone);
     {
         const int64_t per = st_div_up(n > 0 ? n : 1, nseg);
         // (every point in flight at once is the fastest: 95 us; 2048 / 1024 / 512 workgroups per cloud: 112 / 127 / 177 us)
@@ -629,16 +749,28 @@ static int vx_voxelize(const float* xyz, const float* rgb, int64_t n, const int3
     return ST_OK;
 }
 
+// centred_box (device [nseg][6], or NULL = st_voxelize_blocks_seg): the box st_centre_cloud_box_seg left for exactly these
+// points; the bounding-box pass over the cloud is then not launched.  Same results either way.
+extern "C" int st_voxelize_blocks_box_seg(const float* xyz, const float* rgb, int64_t n, const int32_t* seg_off, int nseg,
+                                          double voxel_size, double block_size, double buffer_size, int min_points, int max_blocks,
+                                          int64_t max_voxels, float* feats, int32_t* coords, uint8_t* mask, int64_t* point_index,
+                                          float* block_centres, int32_t* blk_seg, int32_t* seg_vox_off, int32_t* seg_blk_off,
+                                          int64_t* n_voxels_out, int64_t* n_blocks_out, void* ws, int64_t ws_bytes, void* stream_,
+                                          const float* centred_box) {
+    ST_REQUIRE(block_centres != nullptr, "voxelize: block_centres is an output of the blocked call");
+    ST_REQUIRE(nseg == 1 || (blk_seg && seg_blk_off), "voxelize: a batch needs the per-cloud block outputs");
+    return vx_voxelize(xyz, rgb, n, seg_off, nseg, voxel_size, block_size, buffer_size, min_points, max_blocks, max_voxels, feats,
+                       coords, mask, point_index, block_centres, blk_seg, seg_vox_off, seg_blk_off, n_voxels_out, n_blocks_out, ws,
+                       ws_bytes, stream_, 0, centred_box);
+}
 extern "C" int st_voxelize_blocks_seg(const float* xyz, const float* rgb, int64_t n, const int32_t* seg_off, int nseg,
                                       double voxel_size, double block_size, double buffer_size, int min_points, int max_blocks,
                                       int64_t max_voxels, float* feats, int32_t* coords, uint8_t* mask, int64_t* point_index,
                                       float* block_centres, int32_t* blk_seg, int32_t* seg_vox_off, int32_t* seg_blk_off,
                                       int64_t* n_voxels_out, int64_t* n_blocks_out, void* ws, int64_t ws_bytes, void* stream_) {
-    ST_REQUIRE(block_centres != nullptr, "voxelize: block_centres is an output of the blocked call");
-    ST_REQUIRE(nseg == 1 || (blk_seg && seg_blk_off), "voxelize: a batch needs the per-cloud block outputs");
-    return vx_voxelize(xyz, rgb, n, seg_off, nseg, voxel_size, block_size, buffer_size, min_points, max_blocks, max_voxels, feats,
-                       coords, mask, point_index, block_centres, blk_seg, seg_vox_off, seg_blk_off, n_voxels_out, n_blocks_out, ws,
-                       ws_bytes, stream_, 0);
+    return st_voxelize_blocks_box_seg(xyz, rgb, n, seg_off, nseg, voxel_size, block_size, buffer_size, min_points, max_blocks,
+                                      max_voxels, feats, coords, mask, point_index, block_centres, blk_seg, seg_vox_off, seg_blk_off,
+                                      n_voxels_out, n_blocks_out, ws, ws_bytes, stream_, nullptr);
 }
 
 // Whole-cloud voxelisation, the training / evaluation side's data path: replaces TreeDataset.process_cloud's PointToVoxel call

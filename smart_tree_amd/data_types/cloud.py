@@ -46,6 +46,9 @@ class Cloud:
     # [seg_off[b], seg_off[b+1]) -- the batch index the reference writes into coords[:,0] (model/sparse.py:40-61), carried
     # from the input clouds to the skeletons so that a whole batch goes through ONE set of kernel launches.
     seg_off: Optional[torch.Tensor] = None  # [B+1] int32 on the cloud's device; None = a single cloud
+    # Set by CentreCloud alone: [B,6] float32 min / max xyz of every cloud as it left the centring kernel.  The voxeliser takes it
+    # instead of reducing the box again; every operation that makes other points out of these (filter, scale, ...) drops it.
+    centred_box: Optional[torch.Tensor] = None
 
     def __post_init__(self):
         n = self.xyz.shape[0]
@@ -79,6 +82,7 @@ class Cloud:
             raise ValueError("Cloud.filter: a batch of clouds (seg_off) needs a boolean mask or a strictly increasing index; "
                              "split() the batch before reordering / resampling its points")
         out = self._map(lambda t: t.index_select(0, mask))
+        out.centred_box = None
         if self.seg_off is not None:  # batched: the clouds' new ranges (`mask` must keep the points in order)
             out.seg_off = torch.searchsorted(mask, self.seg_off.to(mask.dtype)).to(torch.int32)
         return out
@@ -120,6 +124,8 @@ class Cloud:
         out = self._map(lambda t: t.to(device))
         if self.seg_off is not None:
             out.seg_off = self.seg_off.to(device)
+        if self.centred_box is not None:
+            out.centred_box = self.centred_box.to(device)
         return out
 
     def cpu(self) -> "Cloud":
@@ -195,7 +201,7 @@ class Cloud:
     @staticmethod
     def from_numpy(**arrays) -> "Cloud":
         """Keys as in the reference's .npz clouds (cloud.py:233-252); legacy key `vector`."""
-        known = {f.name for f in fields(Cloud)} - {"filename"}
+        known = {f.name for f in fields(Cloud)} - {"filename", "centred_box"}
         kw = {}
         for key, value in arrays.items():
             if key in known:

@@ -33,9 +33,12 @@ class CentreCloud(Augmentation):
             out = torch.empty_like(xyz)
             nseg = cloud.n_seg
             ws = _lib.workspace(256 + 24 * nseg, xyz.device)
-            _lib.check(L.st_centre_cloud_seg(_lib.ptr(xyz), xyz.shape[0], _lib.ptr(cloud.seg_off), nseg, _lib.ptr(out), _lib.ptr(ws),
-                                             ws.numel(), _lib.stream(xyz.device)))
-            return Cloud(out, cloud.rgb, seg_off=cloud.seg_off)
+            # the box of the centred clouds stays on the device for the voxeliser (SingleTreeInference), which then skips its own
+            # bounding-box pass over the points
+            box = torch.empty((nseg, 6), dtype=torch.float32, device=xyz.device) if xyz.shape[0] > 0 else None
+            _lib.check(L.st_centre_cloud_box_seg(_lib.ptr(xyz), xyz.shape[0], _lib.ptr(cloud.seg_off), nseg, _lib.ptr(out), _lib.ptr(ws),
+                                                 ws.numel(), _lib.stream(xyz.device), _lib.ptr(box)))
+            return Cloud(out, cloud.rgb, seg_off=cloud.seg_off, centred_box=box)
         if cloud.seg_off is not None:
             raise _lib.StError("batched clouds are centred on the GPU only")
         centre, half = cloud.bbox  # host tensors (e.g. before upload): plain torch, as the reference writes it

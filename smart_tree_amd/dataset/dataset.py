@@ -40,19 +40,25 @@ class VoxelBatch:
 
 def voxelize_blocks(xyz: torch.Tensor, rgb: Optional[torch.Tensor], voxel_size: float, block_size: float = 4,
                     buffer_size: float = 0.4, min_points: int = 20, max_blocks: int = 4096,
-                    seg_off: Optional[torch.Tensor] = None) -> VoxelBatch:
+                    seg_off: Optional[torch.Tensor] = None, centred_box: Optional[torch.Tensor] = None) -> VoxelBatch:
     """seg_off ([B+1] int32, device): xyz holds B independent clouds; blocks are numbered cloud by cloud and the part of
-    every cloud equals the one-cloud result (block index shifted, `point_index` into the batched array)."""
+    every cloud equals the one-cloud result (block index shifted, `point_index` into the batched array).
+    centred_box ([B,6] float32, device): `Cloud.centred_box` of exactly these points (CentreCloud was the step before): the
+    voxeliser takes the box instead of reducing it from the points again; the result does not depend on it."""
     L = _lib.lib()
     dev = xyz.device
     xyz = xyz.contiguous().float()
     rgb = rgb.contiguous().float() if rgb is not None else None
     n = xyz.shape[0]
     nseg = 1 if seg_off is None else int(seg_off.shape[0]) - 1
-    return _voxelize_blocks(xyz, rgb, n, nseg, seg_off, voxel_size, block_size, buffer_size, min_points, max_blocks)
+    if centred_box is not None:
+        centred_box = centred_box.contiguous().float()
+        if tuple(centred_box.shape) != (nseg, 6):
+            raise ValueError(f"centred_box must be [{nseg},6], got {tuple(centred_box.shape)}")
+    return _voxelize_blocks(xyz, rgb, n, nseg, seg_off, voxel_size, block_size, buffer_size, min_points, max_blocks, centred_box)
 
 
-def _voxelize_blocks(xyz, rgb, n, nseg, seg_off, voxel_size, block_size, buffer_size, min_points, max_blocks):
+def _voxelize_blocks(xyz, rgb, n, nseg, seg_off, voxel_size, block_size, buffer_size, min_points, max_blocks, centred_box=None):
     L = _lib.lib()
     dev = xyz.device
     per_cloud_blocks = max_blocks
@@ -74,11 +80,11 @@ def _voxelize_blocks(xyz, rgb, n, nseg, seg_off, voxel_size, block_size, buffer_
         pidx = torch.empty((cap,), dtype=torch.int64, device=dev)
         centres = torch.empty((max_blocks, 3), dtype=torch.float32, device=dev)
         ws = _lib.workspace(L.st_voxelize_workspace_bytes_seg(n, max_blocks, cap, nseg), dev)
-        rc = L.st_voxelize_blocks_seg(_lib.ptr(xyz), _lib.ptr(rgb), n, _lib.ptr(seg_off), nseg, float(voxel_size),
-                                      float(block_size), float(buffer_size), int(min_points), int(max_blocks), cap,
-                                      _lib.ptr(feats), _lib.ptr(coords), _lib.ptr(mask), _lib.ptr(pidx), _lib.ptr(centres),
-                                      _lib.ptr(blk_seg), _lib.ptr(seg_vox), _lib.ptr(seg_blk), ctypes.byref(n_vox),
-                                      ctypes.byref(n_blk), _lib.ptr(ws), ws.numel(), _lib.stream(dev))
+        rc = L.st_voxelize_blocks_box_seg(_lib.ptr(xyz), _lib.ptr(rgb), n, _lib.ptr(seg_off), nseg, float(voxel_size),
+                                          float(block_size), float(buffer_size), int(min_points), int(max_blocks), cap,
+                                          _lib.ptr(feats), _lib.ptr(coords), _lib.ptr(mask), _lib.ptr(pidx), _lib.ptr(centres),
+                                          _lib.ptr(blk_seg), _lib.ptr(seg_vox), _lib.ptr(seg_blk), ctypes.byref(n_vox),
+                                          ctypes.byref(n_blk), _lib.ptr(ws), ws.numel(), _lib.stream(dev), _lib.ptr(centred_box))
         if rc == 0 or b"exceed max_voxels" not in L.st_last_error():
             break
     if rc != 0 and (b"bounding box of a cloud has more than" in L.st_last_error() or b"exceed max_blocks" in L.st_last_error()) \
@@ -86,7 +92,7 @@ def _voxelize_blocks(xyz, rgb, n, nseg, seg_off, voxel_size, block_size, buffer_
         # a plot larger than the default block table (8 x max_blocks cells, >= 32768: e.g. a stray point far away, or hundreds
         # of metres of forest): the reference's torch.unique handles any extent -- retry with a larger table
         return _voxelize_blocks(xyz, rgb, n, nseg, seg_off, voxel_size, block_size, buffer_size, min_points,
-                                min(per_cloud_blocks * 8, 65535))
+                                min(per_cloud_blocks * 8, 65535), centred_box)
     _lib.check(rc)
     m, b = n_vox.value, n_blk.value
     if n > 0:
@@ -202,7 +208,7 @@ class SingleTreeInference:
         self.min_points = min_points
         self.file_name = file_name
         self.batch = voxelize_blocks(cloud.xyz, cloud.rgb, voxel_size, block_size, buffer_size, min_points,
-                                     seg_off=cloud.seg_off)
+                                     seg_off=cloud.seg_off, centred_box=getattr(cloud, "centred_box", None))
         self.block_centres = self.batch.block_centres
 
     def __len__(self) -> int:

@@ -77,7 +77,7 @@ class ModelInference:
     def forward(self, cloud: Cloud, return_masked: bool = True) -> Cloud:
         cloud = cloud.to_device(self.device)
         if cloud.rgb is None:
-            cloud = Cloud(cloud.xyz, torch.zeros_like(cloud.xyz), seg_off=cloud.seg_off)
+            cloud = Cloud(cloud.xyz, torch.zeros_like(cloud.xyz), seg_off=cloud.seg_off, centred_box=cloud.centred_box)
         with profiling.stage("voxelize"):
             if self.blocking == "whole":  # SURVEY 8f.2, opt-in: one grid per cloud, no halo duplicates, every voxel is "inner"
                 vb = voxelize_cloud(cloud.xyz, cloud.rgb, self.voxel_size, seg_off=cloud.seg_off)

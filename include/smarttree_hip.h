@@ -221,6 +221,32 @@ int st_post_process(int n_trees, const int32_t* tree_off, const int32_t* parent,
 int st_points_to_nearest_tube(const float* pts, int64_t n, const float* a, const float* b, const float* r1, const float* r2,
                               int64_t m, float* vec, int64_t* idx, float* rad, void* stream);
 
+/* ---- skeleton evaluation against ground truth (csrc/skeleton_eval.hip) ---------------------------------
+ * replaces: sample_tubes (data_types/tube.py:53-74): per tube arange(0, len, len / n) points with linspace radii, a host loop
+ * replaces: TreeSkeleton.sample_skeleton (data_types/tree.py:52-53): sample_tubes over to_tubes()
+ * replaces: TreeSkeleton.point_to_skeleton (data_types/tree.py:65-71): the dense N x M projection, here by NEAREST AXIS
+ * Tubes are (a, b [m,3]; r1, r2 [m]) float32 in to_tubes() order.
+ * Sampling: len = sqrtf(dot(v, v)), v = b - a; n = ceil((double)len / spacing), 0 for a zero or non-finite length; sample
+ * k < n is a + v * f with radius r1 + (r2 - r1) * f, f = (float)k / (float)n; tube i owns samples [off[i], off[i] + n_i).
+ * st_sample_tubes_count writes n and the exclusive offsets (int32 [m] each) and reads the total back (refused from 2^31);
+ * st_sample_tubes_fill (enqueue-only) writes pts [total,3], rad [total], tube_of [total] int32, each nullable.
+ * Matching: t = clip01(dot(ap, ab) * (1 / dot(ab, ab))), a zero-length tube is the point a; d2 = |a + t ab - p|^2; the
+ * first tube with the smallest finite d2 wins (none: idx = -1, dist = +inf, tube_rad = NaN).  Per sample, nullable:
+ * dist = sqrtf(d2), idx (int32), tube_rad = (1 - t) r1 + t r2.  tally (device, 8 * n_thr + 32 bytes): int64 hits[n_thr]
+ * = samples with idx >= 0 and dist <= thr[j] * ref (ref_mode 0: the sample's rad, 1: the winner's tube_rad), then double
+ * sums[4] = sum dist, sum |rad - tube_rad|, sum |rad - tube_rad| / ref, number of samples with idx >= 0.  The tally is
+ * bit-identical from run to run (integer atomics; float64 partials per workgroup added in workgroup order).  1 <= n_thr <= 32;
+ * thr is a device array.  Enqueue-only; n == 0 zeroes the tally. */
+int64_t st_sample_tubes_workspace_bytes(int64_t m);
+int st_sample_tubes_count(const float* a, const float* b, int64_t m, double spacing, int32_t* count, int32_t* off,
+                          int64_t* total_host, void* ws, int64_t ws_bytes, void* stream);
+int st_sample_tubes_fill(const float* a, const float* b, const float* r1, const float* r2, int64_t m, double spacing,
+                         const int32_t* off, int64_t total, float* pts, float* rad, int32_t* tube_of, void* stream);
+int64_t st_skeleton_match_workspace_bytes(int64_t n);
+int st_skeleton_match(const float* pts, const float* rad, int64_t n, const float* a, const float* b, const float* r1,
+                      const float* r2, int64_t m, const float* thr, int n_thr, int ref_mode, float* dist, int32_t* idx,
+                      float* tube_rad, void* tally, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- batched forms: B independent clouds in ONE launch set -------------------------------------------
  * replaces: the batch dimension of the reference's data path -- model/sparse.py:40-61 (batch_collate writes the
  *           sample index into coords[:,0]) and model/model_inference.py:62-78 (one forward per collated batch) --

@@ -69,6 +69,11 @@ SIGNATURES = {
     "st_assemble_branches": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, c_int64, c_int64, P, P, c_int64, P]),
     "st_points_to_nearest_tube": (c_int, [P, c_int64, P, P, P, P, c_int64, P, P, P, P]),
     "st_post_process": (c_int, [c_int, P, P, P, P, P, P, P, P, P, P, P, c_int, c_float, c_float, c_int, c_int, c_int, P]),
+    "st_sample_tubes_workspace_bytes": (I64, [I64]),
+    "st_sample_tubes_count": (c_int, [P, P, I64, c_double, P, P, ctypes.POINTER(I64), P, I64, P]),
+    "st_sample_tubes_fill": (c_int, [P, P, P, P, I64, c_double, P, I64, P, P, P, P]),
+    "st_skeleton_match_workspace_bytes": (I64, [I64]),
+    "st_skeleton_match": (c_int, [P, P, I64, P, P, P, P, I64, P, c_int, c_int, P, P, P, P, P, I64, P]),
     "st_skeleton_workspace_bytes": (I64, [I64, I64]),
     # batched forms (B clouds per launch set)
     "st_centre_cloud_seg": (c_int, [P, I64, P, c_int, P, P, I64, P]),
@@ -133,6 +138,7 @@ ENQUEUE_ONLY = frozenset({
     "st_loss_backward", "st_sparse_conv_wgrad_workspace_bytes", "st_sparse_conv_wgrad",
     "st_sparse_conv_h_fwd", "st_sparse_conv_wgrad_h_workspace_bytes", "st_sparse_conv_wgrad_h", "st_move_rows_h",
     "st_bn_workspace_bytes", "st_bn_stats", "st_bn_apply", "st_bn_backward_stats", "st_bn_backward_apply",
+    "st_sample_tubes_workspace_bytes", "st_sample_tubes_fill", "st_skeleton_match_workspace_bytes", "st_skeleton_match",
 })
 
 

@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 
 from .branch import BranchSkeleton
-from .tube import Tube
+from .tube import Tube, sample_tubes
 
 
 def offset_to_nearest_tube(pt: torch.Tensor, chain_xyz: torch.Tensor, chain_radii: torch.Tensor) -> torch.Tensor:
@@ -49,6 +49,10 @@ class TreeSkeleton:
 
     def to_tubes(self) -> List[Tube]:
         return [t for b in self.branches.values() for t in b.to_tubes()]
+
+    def sample_skeleton(self, spacing):
+        """(pts [N,3], radius [N]) every `spacing` along the tubes (reference tree.py:52-53)."""
+        return sample_tubes(self.to_tubes(), spacing)
 
     def repair(self) -> None:
         """Vectorised over the parent's tube chain (no per-tube objects): same arithmetic as
@@ -95,6 +99,13 @@ class TreeSkeleton:
 @dataclass
 class DisjointTreeSkeleton:
     skeletons: List[TreeSkeleton]
+
+    def to_tubes(self) -> List[Tube]:
+        return [t for s in self.skeletons for t in s.to_tubes()]
+
+    def sample_skeleton(self, spacing):
+        """The samples of every skeleton, in skeleton order."""
+        return sample_tubes(self.to_tubes(), spacing)
 
     def prune(self, min_radius, min_length) -> None:
         if self.skeletons:

@@ -29,7 +29,8 @@ extern "C" {
 /* 101 (round 6): st_abi_entries added; stats_host of the skeleton calls is 16 x int64 (8 before 100) and their tuning array
  * 24 x int64 -- a caller built against an older header must check st_abi_entries before passing shorter arrays.
  * 105: st_centre_cloud_box_seg and st_voxelize_blocks_box_seg added (no existing signature or st_abi_entries value changed);
- * st_component_csr_knn_workspace_bytes asks for one more int32 per table entry. */
+ * st_component_csr_knn_workspace_bytes asks for one more int32 per table entry.
+ * 107: st_synth_points_seg and st_synth_philox added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -411,6 +412,26 @@ int st_bn_backward_stats(const void* x, const void* dy, int half, int64_t n, int
                          double* out, void* ws, int64_t ws_bytes, void* stream);
 int st_bn_backward_apply(const void* x, const void* dy, int half, int64_t n, int C, const float* mean, const float* invstd,
                          const float* gamma, const double* sums, const double* count, void* dx, void* stream);
+
+/* ---- dataset: labelled synthetic trees sampled on the device (csrc/synthetic.hip) ------------------------
+ * replaces: the reference's external `synthetic-trees` download as the source of labelled trees, and the host sampler
+ *           smart_tree_amd/synthetic.py:sample_tree_cloud plus the upload of its result.
+ * st_synth_points_seg generates B <= 64 trees in one launch.  Device arrays, the trees' rows concatenated: table [S,16] float32
+ * (ax ay az ra | bx by bz rb | ux uy uz branch-id as int32 bits | vx vy vz 0), cdf [S] uint32 (floor(2^32 * cumulative lateral
+ * area / total), a tree's last entry 0xFFFFFFFF), tips [T,3] float32.  HOST arrays (they travel as kernel arguments, so the call
+ * checks them and is still enqueue-only): tab_off, tip_off, pt_off [B+1] int32 (tree s owns rows [tab_off[s], tab_off[s+1]) and
+ * points [pt_off[s], pt_off[s+1]), pt_off[0] = 0), seeds [B] uint64, fol_thr [B] uint32 (min(floor(fraction * 2^32), 2^32 - 1);
+ * all ones = every point), noise and foliage_sigma [B] float32.  Point i of a tree draws from Philox4x32-10 with key = the two
+ * halves of the seed and counter (i, k, 0, 0), k = 0, 1; the use of each word and the float32 evaluation order are the table in
+ * the header comment of csrc/synthetic.hip.  Outputs (device, each nullable): xyz, medial_vector [N,3], class_l [N] float32
+ * (1 = foliage), branch_ids [N] int32 (-1 foliage), segment [N] int32 (row of the batched table, -1 foliage); N = pt_off[B].
+ * Refused, nothing written: B > 64, a negative or decreasing offset, a tree with points and no segments.
+ * st_synth_philox (host, for tests): out[4] = Philox4x32-10(counter[4], key[2]), the function the kernel calls. */
+int st_synth_points_seg(const float* table, const int32_t* tab_off, const uint32_t* cdf, const float* tips, const int32_t* tip_off,
+                        const int32_t* pt_off, int B, const uint64_t* seeds, const uint32_t* fol_thr, const float* noise,
+                        const float* foliage_sigma, float* xyz, float* medial_vector, float* class_l, int32_t* branch_ids,
+                        int32_t* segment, void* stream);
+void st_synth_philox(const uint32_t* counter, const uint32_t* key, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -75,6 +75,8 @@ SIGNATURES = {
     "st_skeleton_match_workspace_bytes": (I64, [I64]),
     "st_skeleton_match": (c_int, [P, P, I64, P, P, P, P, I64, P, c_int, c_int, P, P, P, P, P, I64, P]),
     "st_skeleton_workspace_bytes": (I64, [I64, I64]),
+    "st_synth_points_seg": (c_int, [P, P, P, P, P, P, c_int, P, P, P, P, P, P, P, P, P, P]),
+    "st_synth_philox": (None, [P, P, P]),
     # batched forms (B clouds per launch set)
     "st_centre_cloud_seg": (c_int, [P, I64, P, c_int, P, P, I64, P]),
     "st_centre_cloud_box_seg": (c_int, [P, I64, P, c_int, P, P, I64, P, P]),
@@ -139,6 +141,7 @@ ENQUEUE_ONLY = frozenset({
     "st_sparse_conv_h_fwd", "st_sparse_conv_wgrad_h_workspace_bytes", "st_sparse_conv_wgrad_h", "st_move_rows_h",
     "st_bn_workspace_bytes", "st_bn_stats", "st_bn_apply", "st_bn_backward_stats", "st_bn_backward_apply",
     "st_sample_tubes_workspace_bytes", "st_sample_tubes_fill", "st_skeleton_match_workspace_bytes", "st_skeleton_match",
+    "st_synth_points_seg", "st_synth_philox",
 })
 
 

@@ -37,7 +37,7 @@ import torch
 import torch.distributed as dist
 import yaml
 
-from ..config import apply_overrides, instantiate, load_yaml, resolve
+from ..config import _REF, apply_overrides, instantiate, load_yaml, resolve
 from ..data_types.cloud import Cloud
 from . import data_parallel as dp
 from .helper import get_batch, model_output_to_labelled_clds
@@ -184,17 +184,34 @@ class StopPolicy:
         return Decision(bool(self.lr_decay), save, stop)
 
 
+def _refers_to(node, key: str) -> bool:
+    """Some value of the configuration interpolates `${key}`."""
+    if isinstance(node, dict):
+        return any(_refers_to(v, key) for v in node.values())
+    if isinstance(node, list):
+        return any(_refers_to(v, key) for v in node)
+    return isinstance(node, str) and any(m.strip() == key for m in _REF.findall(node))
+
+
 def load_training_config(overrides=()) -> dict:
-    """conf/training.yaml (or, with `resume=<run_dir>`, that run's config.yaml) + overrides, `device: auto` decided, then the
-    interpolations resolved.  A resumed run writes into the run it continues."""
+    """conf/training.yaml (or `config=<name>`: conf/<name>.yaml; or, with `resume=<run_dir>`, that run's config.yaml) + overrides,
+    `device: auto` decided, then the interpolations resolved.  `directory` and `json_path` are demanded when the configuration
+    refers to them (conf/training.yaml does, conf/training_synthetic.yaml does not).  A resumed run writes into the run it
+    continues."""
     overrides = list(overrides)
-    base = CONF
+    base, named = CONF, None
     for item in overrides:
         key, _, value = item.lstrip("+").partition("=")
         if key == "resume" and yaml.safe_load(value):
             base = Path(str(yaml.safe_load(value))) / "config.yaml"
+        elif key == "config" and yaml.safe_load(value):  # another bundled configuration: conf/<name>.yaml
+            named = CONF.parent / f"{yaml.safe_load(value)}.yaml"
+            if not named.is_file():
+                raise ValueError(f"train-smart-tree: no bundled configuration '{yaml.safe_load(value)}' ({named})")
+    if named is not None and base is CONF:  # a resumed run keeps the configuration it was started with
+        base = named
     cfg = apply_overrides(load_yaml(base), overrides)
-    missing = [k for k in REQUIRED if cfg.get(k) in (None, "???", "")]
+    missing = [k for k in REQUIRED if cfg.get(k) in (None, "???", "") and _refers_to(cfg, k)]
     if missing:
         raise ValueError(f"train-smart-tree: {' and '.join(missing)} not set: pass " + " ".join(f"{k}=..." for k in missing))
     if cfg.get("device", "auto") == "auto":  # under torchrun: this rank's GPU
@@ -310,6 +327,9 @@ def run(cfg: dict, group=None) -> dict:
     for epoch in range(start, cfg["num_epoch"] if not stopped else start):
         t0 = time.perf_counter()
         lr = optimizer.param_groups[0]["lr"]
+        for loader in (train_loader, val_loader, test_loader):  # a dataset that generates its trees: this epoch's
+            if hasattr(loader.dataset, "set_epoch"):
+                loader.dataset.set_epoch(epoch)
         train = train_epoch(train_loader, model, optimizer, loss_fn, device, fp16=fp16, scaler=scaler, **ep_kw)
         val = eval_epoch(val_loader, model, loss_fn, device, fp16=fp16, **ep_kw)
         test = eval_epoch(test_loader, model, loss_fn, device, fp16=fp16, **ep_kw)

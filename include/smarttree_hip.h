@@ -30,7 +30,8 @@ extern "C" {
  * 24 x int64 -- a caller built against an older header must check st_abi_entries before passing shorter arrays.
  * 105: st_centre_cloud_box_seg and st_voxelize_blocks_box_seg added (no existing signature or st_abi_entries value changed);
  * st_component_csr_knn_workspace_bytes asks for one more int32 per table entry.
- * 107: st_synth_points_seg and st_synth_philox added (no existing signature changed). */
+ * 107: st_synth_points_seg and st_synth_philox added (no existing signature changed).
+ * 108: st_prediction_metrics and its three size queries added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -432,6 +433,37 @@ int st_synth_points_seg(const float* table, const int32_t* tab_off, const uint32
                         const float* foliage_sigma, float* xyz, float* medial_vector, float* class_l, int32_t* branch_ids,
                         int32_t* segment, void* stream);
 void st_synth_philox(const uint32_t* counter, const uint32_t* key, uint32_t* out);
+
+/* ---- evaluation: per-point prediction metrics (csrc/prediction_metrics.hip) ------------------------------
+ * replaces: nothing in the reference (no evaluation of the network's outputs exists there); reads the rows st_loss_forward
+ *           reads, once: radius [n], direction [n,3], class_l [n,C] (predictions), targets [n,5] = radius, direction xyz, class id,
+ *           mask [n] bytes or NULL.  Segment s (a tree of the batch) owns rows [seg_off_host[s], seg_off_host[s+1]); NULL with
+ *           n_seg = 1 is the one segment [0, n).  seg_off_host, thr_host [n_thr] and edges_host [n_edges] are HOST arrays (they
+ *           travel as kernel arguments: the call checks them and is still enqueue-only; nothing is read back).
+ * Per selected row (mask NULL or non-zero), float32 in the order written in the header of csrc/prediction_metrics.hip:
+ *   target class tc = (int)t[4], valid iff t[4] > -1 && t[4] < C (else bad_class, nothing more); predicted class pc = the first
+ *   NaN logit if any, otherwise the first largest; confusion[tc][pc] (target row, prediction column).  For vector rows
+ *   (vector_class < 0 or tc == vector_class): r_gt = t[0], r_pred = target_radius_log ? expf(radius) : radius, dr = |r_pred - r_gt|,
+ *   ang = acosf(clamp(p^ . q^, -1, 1)) with norms clamped at 1e-8f, err = |r_pred p^ - r_gt q^| (the distance between the
+ *   predicted and the labelled medial point); a row with a non-finite dr, dr / r_gt, ang, err or err / r_gt counts in
+ *   bad_vector only; otherwise within[j] counts err <= thr[j] * r_gt and the row falls into radius bin #{e: r_gt >= edges[e]}.
+ * Record of a segment, n_bins = n_edges + 1 (both tallies are DEVICE arrays of n_seg records, fully written by the call):
+ *   tally_ints  int64   confusion[C*C] | bad_class | vector_rows | bad_vector | rows | within[n_thr] | bin_count[n_bins]
+ *   tally_sums  double  sum dr | sum dr/r_gt | sum ang | sum err | sum err/r_gt | bin_dr_rel[n_bins] | bin_err_rel[n_bins]
+ *   (rows = selected rows; vector_rows = the rows in the sums).  st_prediction_metrics_tally_ints / _tally_sums give the entries
+ *   of one record (-1 beyond the limits).  Integer atomics and float64 partials added in a fixed order: a segment's record is bit
+ *   for bit the record of the same rows evaluated alone, and two calls give the same bits.  n == 0 or an empty segment: zeros.
+ * Limits: 1 <= C <= 16, n_thr <= 16, n_bins <= 16, 1 <= n_seg <= st_abi_entries(2).  Refused, nothing launched or written: a limit
+ *   exceeded, target_cols != 5, edges not finite or not strictly ascending, a NaN threshold, offsets that decrease, do not start
+ *   at 0 or do not end at n, a null input with n > 0, a workspace below st_prediction_metrics_workspace_bytes(n, n_seg, n_bins). */
+int64_t st_prediction_metrics_tally_ints(int n_classes, int n_thr, int n_bins);
+int64_t st_prediction_metrics_tally_sums(int n_bins);
+int64_t st_prediction_metrics_workspace_bytes(int64_t n, int n_seg, int n_bins);
+int st_prediction_metrics(const float* radius, const float* direction, const float* class_l, int n_classes,
+                          const float* targets, int target_cols, const uint8_t* mask, int64_t n,
+                          const int64_t* seg_off_host, int n_seg, int vector_class, int target_radius_log,
+                          const float* thr_host, int n_thr, const float* edges_host, int n_edges,
+                          int64_t* tally_ints, double* tally_sums, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

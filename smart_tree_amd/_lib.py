@@ -77,6 +77,10 @@ SIGNATURES = {
     "st_skeleton_workspace_bytes": (I64, [I64, I64]),
     "st_synth_points_seg": (c_int, [P, P, P, P, P, P, c_int, P, P, P, P, P, P, P, P, P, P]),
     "st_synth_philox": (None, [P, P, P]),
+    "st_prediction_metrics_tally_ints": (I64, [c_int, c_int, c_int]),
+    "st_prediction_metrics_tally_sums": (I64, [c_int]),
+    "st_prediction_metrics_workspace_bytes": (I64, [I64, c_int, c_int]),
+    "st_prediction_metrics": (c_int, [P, P, P, c_int, P, c_int, P, I64, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, I64, P]),
     # batched forms (B clouds per launch set)
     "st_centre_cloud_seg": (c_int, [P, I64, P, c_int, P, P, I64, P]),
     "st_centre_cloud_box_seg": (c_int, [P, I64, P, c_int, P, P, I64, P, P]),
@@ -142,6 +146,7 @@ ENQUEUE_ONLY = frozenset({
     "st_bn_workspace_bytes", "st_bn_stats", "st_bn_apply", "st_bn_backward_stats", "st_bn_backward_apply",
     "st_sample_tubes_workspace_bytes", "st_sample_tubes_fill", "st_skeleton_match_workspace_bytes", "st_skeleton_match",
     "st_synth_points_seg", "st_synth_philox",
+    "st_prediction_metrics_tally_ints", "st_prediction_metrics_tally_sums", "st_prediction_metrics_workspace_bytes", "st_prediction_metrics",
 })
 
 

@@ -20,6 +20,7 @@ import torch
 
 from ..data_types.tree import DisjointTreeSkeleton, TreeSkeleton
 from ..data_types.tube import sample_tubes_device
+from .prediction import PredictionTally, derive_metrics, prediction_tally, segment_offsets  # noqa: F401  (per-point predictions)
 
 DEFAULT_THRESHOLDS = tuple(round(0.1 * k, 1) for k in range(1, 11))
 MAX_THRESHOLDS = 32

@@ -13,6 +13,9 @@ The `train-smart-tree` run (train.py:166-262 with conf/training.yaml): `main(arg
 [key=value ...]` loads `conf/training.yaml` (smart_tree_amd/config.py), trains with the epochs above and writes `config.yaml`,
 `metrics.jsonl`, `<run_name>_model_weights.pt` (each new best), `last.pt` (every epoch) and `captures/` into `run_dir`;
 `resume=<run_dir>` continues from that run's `last.pt`.  `StopPolicy` holds the best / early-stop / scheduler decisions.
+`prediction_metrics=true` (or a mapping of `evaluation.prediction_tally` keywords; no shipped configuration sets it) adds
+`validation_metrics` and `test_metrics` to every line of `metrics.jsonl`: accuracy, IoU, radius and medial-point errors of the
+predictions (`eval_epoch(metrics=...)`).  The best checkpoint is still chosen by the validation loss.
 
 Data parallel (model/data_parallel.py, model/sync_bn.py): `train_epoch` / `eval_epoch(..., group=g)` take rank g's share of
 every global batch, synchronise BatchNorm (the model must have gone through `sync_bn.convert_sync_batchnorm`), weight the loss
@@ -117,14 +120,30 @@ def train_epoch(data_loader, model, optimizer, loss_fn, device=torch.device("cud
     return _mean(sums, count)
 
 
+def _metrics_keywords(metrics, loss_fn) -> dict:
+    """`prediction_tally`'s keywords for an epoch: `metrics` as given, with the loss's row selection (`vector_class`,
+    `target_radius_log` of a `functools.partial` loss_fn) where `metrics` does not set it."""
+    kw = {k: v for k, v in (getattr(loss_fn, "keywords", None) or {}).items() if k in ("vector_class", "target_radius_log")}
+    kw.update(metrics)
+    return kw
+
+
 @torch.no_grad()
-def eval_epoch(data_loader, model, loss_fn, device=torch.device("cuda"), *, fp16=False, group=None) -> dict:
+def eval_epoch(data_loader, model, loss_fn, device=torch.device("cuda"), *, fp16=False, group=None, metrics=None) -> dict:
     """train.py:61-84: the losses in eval mode (running BatchNorm statistics), no gradients; the model is left in train mode.
     fp16=True: under float16 autocast, as train_epoch.  group: each rank evaluates its share of every global batch and the
-    per-batch values are the global count-weighted means."""
+    per-batch values are the global count-weighted means.
+    metrics: a dict of `evaluation.prediction_tally` keywords ({} = its defaults) tallies every batch's predictions in one more
+    HIP pass, adds the tallies on the device (all-reduced once at the end under `group`) and returns their
+    `PredictionTally.metrics()` under "metrics" (None for a loader without batches).  None (the default): nothing of this."""
     device = torch.device(device)
     if group is not None:
         data_loader = _data_parallel(data_loader, model, loss_fn, group)
+    if metrics is not None:
+        from ..evaluation.prediction import prediction_tally
+
+        metrics = _metrics_keywords(metrics, loss_fn)
+    tally = None
     model.eval()
     sums, count = {}, 0
     for sp_input, targets, mask in _batches(data_loader, device, fp16, model):
@@ -137,8 +156,16 @@ def eval_epoch(data_loader, model, loss_fn, device=torch.device("cuda"), *, fp16
         for k, v in values.items():
             sums[k] = sums.get(k, 0.0) + v
         count += 1
+        if metrics is not None:
+            batch = prediction_tally(preds, targets, mask, **metrics)
+            tally = batch if tally is None else tally + batch
     model.train()
-    return _mean(sums, count)
+    out = _mean(sums, count)
+    if metrics is not None:
+        if tally is not None and group is not None:
+            tally = tally.all_reduce(group)
+        out["metrics"] = tally.metrics() if tally is not None else None
+    return out
 
 
 @torch.no_grad()
@@ -285,6 +312,8 @@ def run(cfg: dict, group=None) -> dict:
     if lead:
         (run_dir / "config.yaml").write_text(yaml.safe_dump(cfg, sort_keys=False))
     ep_kw = {"group": group} if group is not None else {}
+    pm = cfg.get("prediction_metrics")  # absent / false: off; true: prediction_tally's defaults; a mapping: its keywords
+    ev_kw = dict(ep_kw) if pm in (None, False) else {**ep_kw, "metrics": {} if pm is True else dict(pm)}
 
     torch.manual_seed(42)
     torch.cuda.manual_seed_all(42)
@@ -331,8 +360,9 @@ def run(cfg: dict, group=None) -> dict:
             if hasattr(loader.dataset, "set_epoch"):
                 loader.dataset.set_epoch(epoch)
         train = train_epoch(train_loader, model, optimizer, loss_fn, device, fp16=fp16, scaler=scaler, **ep_kw)
-        val = eval_epoch(val_loader, model, loss_fn, device, fp16=fp16, **ep_kw)
-        test = eval_epoch(test_loader, model, loss_fn, device, fp16=fp16, **ep_kw)
+        val = eval_epoch(val_loader, model, loss_fn, device, fp16=fp16, **ev_kw)
+        test = eval_epoch(test_loader, model, loss_fn, device, fp16=fp16, **ev_kw)
+        val_metrics, test_metrics = val.pop("metrics", None), test.pop("metrics", None)
         if cfg["capture_output"] > 0 and (epoch + 1) % cfg["capture_output"] == 0:
             _capture(run_dir, epoch, {"test": test_loader, "validation": val_loader}, model, cfg, device, group)
         if group is not None:
@@ -348,6 +378,8 @@ def run(cfg: dict, group=None) -> dict:
             sink.log({"lr": lr, "seconds": seconds, "best": policy.best}, step=epoch)
             for name, means in (("train", train), ("validation", val), ("test", test)):
                 sink.log({name: {**means, "total": total(means)}}, step=epoch)
+            if "metrics" in ev_kw:
+                sink.log({"validation_metrics": val_metrics, "test_metrics": test_metrics}, step=epoch)
             sink.commit()
         log.info("epoch %d/%d: train %.4f, validation %.4f, test %.4f, lr %.3g, %.2f s%s", epoch + 1, cfg["num_epoch"], total(train),
                  total(val), total(test), lr, seconds, ", weights saved" if decision.save_best else "")

@@ -207,7 +207,12 @@ int st_tree_distance(ST_SKELETON_STAGE_ARGS);
 int st_sample_tree(ST_SKELETON_STAGE_ARGS);
 int64_t st_assemble_workspace_bytes(int64_t cap_b);
 /* counts_host may be NULL: no read-back; the caller takes branches B = stats_host[6] & 0xffffffff and geometry slots
- * P = (stats_host[6] >> 32) + B from st_skeleton_components (totals carried by its last progress read-back) */
+ * P = (stats_host[6] >> 32) + B from st_skeleton_components (totals carried by its last progress read-back).
+ * Capacities: parent / start / length are cap_b long, xyz / rad cap_p.  When B > cap_b or P > cap_p nothing outside them is
+ * read or written: the first min(B, cap_b) branches are laid out (start [cap_b] is always filled), of their geometry the
+ * first cap_p slots, and tree_off [n_comp + 1] is complete.  With counts_host the call then returns ST_ERR_INVALID and
+ * counts_host holds the B and P that were needed; with NULL it returns ST_OK -- the caller vouches for the capacities, or
+ * compares tree_off[n_comp] with cap_b itself. */
 int st_assemble_branches(int n_comp, const int32_t* comp_off, const int32_t* n_branches, const int32_t* branch_parent,
                          const int32_t* branch_off, const int32_t* branch_len, const int32_t* path_verts,
                          const int32_t* vert_order, const float* medial, const float* radius, int32_t* tree_off,

@@ -64,9 +64,9 @@ def prune(tree: OTree, min_radius: float, min_length: float) -> None:
     tree.branches = keep
 
 
-def nearest_tube_offset(pt: np.ndarray, parent: OBranch) -> np.ndarray:
-    """queries.py:89-133 for one point against the parent's tube chain: vector to the projection on the
-    tube that minimises |distance - interpolated radius| (first minimum; NaN counts as minimal)."""
+def nearest_tube(pt: np.ndarray, parent: OBranch):
+    """queries.py:89-133 for one point against the parent's tube chain: (index of the tube that minimises |distance -
+    interpolated radius| -- first minimum; NaN counts as minimal --, every tube's score, vector to the projection on it)."""
     p = pt.reshape(1, 3).astype(F32)
     a, b = parent.xyz[:-1].astype(F32), parent.xyz[1:].astype(F32)
     r1, r2 = parent.radii.reshape(-1)[:-1].astype(F32), parent.radii.reshape(-1)[1:].astype(F32)
@@ -80,17 +80,24 @@ def nearest_tube_offset(pt: np.ndarray, parent: OBranch) -> np.ndarray:
     d = proj - p
     score = np.abs(np.sqrt(_dot(d, d)) - r)
     i = int(np.argmax(np.isnan(score))) if np.isnan(score).any() else int(np.argmin(score))
-    return proj[i] - p[0]
+    return i, score, proj[i] - p[0]
 
 
-def repair(tree: OTree) -> None:
-    """tree.py:73-92."""
+def nearest_tube_offset(pt: np.ndarray, parent: OBranch) -> np.ndarray:
+    return nearest_tube(pt, parent)[2]
+
+
+def repair(tree: OTree, trace=None) -> None:
+    """tree.py:73-92.  trace (a list): gets (tree id, branch id, parent already repaired, chosen tube, scores) per repaired branch."""
     ids = set(b._id for b in tree.branches.values())
+    extracted = {b._id: b.xyz.shape[0] for b in tree.branches.values()}
     for b in tree.branches.values():
         if b.parent_id not in ids:
             continue
         parent = tree.branches[b.parent_id]
-        v = nearest_tube_offset(b.xyz[0], parent)
+        i, score, v = nearest_tube(b.xyz[0], parent)
+        if trace is not None:
+            trace.append((tree._id, b._id, parent.xyz.shape[0] > extracted[parent._id], i, score))
         b.xyz = np.concatenate([(b.xyz[0] + v).reshape(1, 3), b.xyz]).astype(F32)  # tree.py:89-91
         b.radii = np.concatenate([b.radii[[0]], b.radii])
 
@@ -111,13 +118,13 @@ def smooth(tree: OTree, kernel_size: int) -> None:
 
 
 def post_process(trees: List[OTree], prune_skeletons=True, min_radius=0.01, min_length=0.02, repair_skeletons=True,
-                 smooth_skeletons=True, smooth_kernel_size=11) -> None:
-    """pipeline.py:95-106 + DisjointTreeSkeleton (tree.py:164-176): only skeleton 0 is pruned."""
+                 smooth_skeletons=True, smooth_kernel_size=11, trace=None) -> None:
+    """pipeline.py:95-106 + DisjointTreeSkeleton (tree.py:164-176): only skeleton 0 is pruned.  trace: see repair."""
     if prune_skeletons and trees:
         prune(trees[0], min_radius, min_length)
     if repair_skeletons:
         for t in trees:
-            repair(t)
+            repair(t, trace)
     if smooth_skeletons:
         for t in trees:
             smooth(t, smooth_kernel_size)

@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(PP_BLOCK) k_pp_tree(PpArgs A) {
             depth[b] = d;
             if (d > md) md = d;
         }
-        s_maxdepth = md > 32767 ? 32767 : md;
+        s_maxdepth = md;  // depth[] is int32 here: no limit of its own (only l_depth is 16 bits wide, and nb <= 8192 bounds it)
     }
     __syncthreads();
     const int maxdepth = s_maxdepth;
@@ -434,18 +434,25 @@ __global__ void __launch_bounds__(1024) k_asm_trees(AsmArgs A) {  // one workgro
         if (threadIdx.x == 0) s_carry = carry + tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0) { A.tree_off[A.C] = (int32_t)s_carry; A.counts[0] = (int64_t)s_carry; }
+    if (threadIdx.x == 0) {
+        A.tree_off[A.C] = (int32_t)s_carry;
+        A.counts[0] = (int64_t)s_carry;
+        A.counts[1] = 0;  // k_asm_branches adds the slots of the branches beyond cap_b, k_asm_geometry those of the others
+    }
 }
 
 __global__ void __launch_bounds__(256) k_asm_branches(AsmArgs A) {
     const int64_t B = A.tree_off[A.C];
-    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < A.cap_b; b += (int64_t)gridDim.x * blockDim.x) {
+    // every output is cap_b long: a branch beyond the capacity is not laid out, only its slots are counted (for the refusal)
+    const int64_t end = B > A.cap_b ? B : A.cap_b;
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < end; b += (int64_t)gridDim.x * blockDim.x) {
         if (b >= B) { A.len1[b] = 0u; continue; }
         int lo = 0, hi = A.C;  // tree with tree_off[c] <= b < tree_off[c + 1] (empty trees have equal offsets: take the last)
         while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if ((int64_t)A.tree_off[mid] <= b) lo = mid; else hi = mid; }
         const int base = A.comp_off[lo];
         const int slot = base + (int)(b - A.tree_off[lo]);
         const int len = A.branch_len[slot];
+        if (b >= A.cap_b) { atomicAdd((unsigned long long*)&A.counts[1], (unsigned long long)(len + 1)); continue; }
         A.parent[b] = A.branch_parent[slot];
         A.length[b] = len;
         A.len1[b] = (uint32_t)(len + 1);
@@ -455,9 +462,10 @@ __global__ void __launch_bounds__(256) k_asm_branches(AsmArgs A) {
 }
 
 __global__ void __launch_bounds__(256) k_asm_geometry(AsmArgs A) {
-    const int64_t B = A.tree_off[A.C];
+    const int64_t total = A.tree_off[A.C];
+    const int64_t B = total < A.cap_b ? total : A.cap_b;  // the branches that were laid out: start / length / src0 hold no more
     const int64_t P = B > 0 ? (int64_t)A.start[B - 1] + A.length[B - 1] + 1 : 0;
-    if (blockIdx.x == 0 && threadIdx.x == 0) A.counts[1] = P;
+    if (blockIdx.x == 0 && threadIdx.x == 0) A.counts[1] += P;  // + the slots k_asm_branches counted beyond cap_b
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < P && k < A.cap_p; k += (int64_t)gridDim.x * blockDim.x) {
         int64_t lo = 0, hi = B;  // branch with start[b] <= k
         while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)A.start[mid] <= k) lo = mid; else hi = mid; }
@@ -489,6 +497,9 @@ extern "C" int64_t st_assemble_workspace_bytes(int64_t cap_b) {
 // Outputs are sized by the caller to the capacities cap_b (branches; every component-local branch slot is enough:
 // cap_b = m) and cap_p (geometry slots; path vertices + branches <= 2 m); counts_host receives the numbers used
 // (NULL: no read-back -- branches and path vertices + branches are known from st_skeleton_components' stats_host[6]).
+// Too small a capacity writes nothing outside the outputs: the first min(B, cap_b) branches are laid out, of their geometry
+// the first cap_p slots; tree_off [n_comp + 1] is always complete.  With counts_host the call then returns ST_ERR_INVALID
+// naming both counts; without it nobody looks, the caller vouches for the capacities (or compares tree_off[n_comp]).
 extern "C" int st_assemble_branches(int n_comp, const int32_t* comp_off, const int32_t* n_branches, const int32_t* branch_parent,
                                     const int32_t* branch_off, const int32_t* branch_len, const int32_t* path_verts,
                                     const int32_t* vert_order, const float* medial, const float* radius, int32_t* tree_off,

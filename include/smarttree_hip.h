@@ -371,18 +371,19 @@ int st_loss_backward(const float* radius, const float* direction, const float* c
                      double n_vector_rows, double n_class_rows, const float* upstream, float* d_radius, float* d_direction,
                      float* d_class_l, void* stream);
 
-/* ---- training: sparse-convolution weight gradient ---------------------------------------------------
+/* ---- training: sparse-convolution weight gradient, float32 and half features (csrc/sparse_conv_grad.hip) ---------
  * replaces: the weight-gradient half of spconv's backward (what autograd runs through SubMConv3d / SparseConv3d /
  *           SparseInverseConv3d in smart_tree/model/train.py:24-58).  The data gradient is st_sparse_conv_fwd over the transposed
  *           table (smart_tree_amd/model/sparse_grad.py).
  * dw[k][ci][co] = sum over o < n_out with nbr[k][o] >= 0 of cat(x0, x1)[nbr[k][o]][ci] * dy[o][co]; dw is [K][cin][cout] (w's
  * layout in st_sparse_conv_fwd).  nbr NULL = pointwise (K = 1); nbr_stride 0 = n_out; n_out == 0 writes zeros.
- * Deterministic: no float atomics, partial sums per (row chunk, offset) in ws, added in chunk order.  cin + cout <= 8192. */
+ * Deterministic: no float atomics, partial sums per (row chunk, offset) in ws, added in chunk order.  cin + cout <= 8192.
+ * st_sparse_conv_wgrad_h (declared with the half calls below) is the same scheme for half x0 / x1 / dy. */
 int64_t st_sparse_conv_wgrad_workspace_bytes(int K, int cin, int cout, int64_t n_out);
 int st_sparse_conv_wgrad(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
                          int64_t nbr_stride, const float* dy, int cout, float* dw, void* ws, int64_t ws_bytes, void* stream);
 
-/* ---- mixed-precision (autocast float16) training (csrc/sparse_conv_half.hip) ----------------------------
+/* ---- mixed-precision (autocast float16) training (csrc/sparse_conv_half.hip; the weight gradient: csrc/sparse_conv_grad.hip) ----
  * replaces: spconv's half-precision conv forward and backward under torch.cuda.amp.autocast (model/train.py:24-58 with
  *           conf/training.yaml fp16: True): SubMConv3d / SparseConv3d / SparseInverseConv3d, model/model_blocks.py:8-285.
  * st_sparse_conv_h_fwd: y = sum_k cat(x0, x1)[nbr[k]] . W[k]; x0, x1, w [K][cin][cout] (plain layout) and y are IEEE half, the

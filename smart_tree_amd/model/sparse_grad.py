@@ -1,18 +1,20 @@
 """Autograd for the sparse convolution and the row permutation (training).
 
-The reference trains through spconv's backward (smart_tree/model/train.py:24-58).  Here:
-  * data gradient (dgrad): the forward kernel (`sparse_ops.sparse_conv`) over the TRANSPOSED neighbour table with transposed weights
-    -- gather form, no atomics, deterministic (`transposed_table` says which table that is);
-  * weight gradient (wgrad): `st_sparse_conv_wgrad` (csrc/sparse_conv_grad.hip), deterministic;
+The reference trains through spconv's backward (smart_tree/model/train.py:24-58).  Here, in either storage type:
+  * data gradient (dgrad): the forward kernel over the TRANSPOSED neighbour table with transposed weights -- gather form, no
+    atomics, deterministic (`transposed_table` says which table that is);
+  * weight gradient (wgrad): `conv_wgrad`, the one deterministic kernel family of csrc/sparse_conv_grad.hip, float32 sums and a
+    float32 dW for both storage types;
   * `move_rows`: the gather's backward is the scatter and the other way round.
 BatchNorm, ReLU, the residual add, the concat and F.normalize stay torch ops around these.
 
-Half path (mixed-precision training, the reference's `fp16: True`): under `torch.autocast(<device type>, dtype=torch.float16)`, or
-with float16 features, the convolution casts features and weight to half (as spconv's `custom_fwd(cast_inputs=torch.float16)`
-convs do), runs `st_sparse_conv_h_fwd` (csrc/sparse_conv_half.hip) and returns half.  Its backward: the data gradient is the same
-kernel over the transposed table with half W', the weight gradient `st_sparse_conv_wgrad_h` (float32 sums) returned as float32 for
-the float32 master weight -- never rounded to half (spconv would return a half dW that autograd then widens: an intended
-difference).  Autocast to any other dtype keeps the float32 path.
+The two storage types:
+  * float32: `sparse_ops.sparse_conv` and `st_sparse_conv_wgrad`;
+  * half (mixed-precision training, the reference's `fp16: True`): under `torch.autocast(<device type>, dtype=torch.float16)`, or
+    with float16 features, the convolution casts features and weight to half (as spconv's `custom_fwd(cast_inputs=torch.float16)`
+    convs do), runs `sparse_ops.sparse_conv_half` (csrc/sparse_conv_half.hip) and returns half; `st_sparse_conv_wgrad_h` gives the
+    float32 master weight its float32 dW -- never rounded to half (spconv would return a half dW that autograd then widens: an
+    intended difference).  Autocast to any other dtype keeps the float32 path.
 """
 from __future__ import annotations
 
@@ -26,8 +28,13 @@ from . import sparse_ops as ops
 
 def conv_wgrad(x0: torch.Tensor, x1: Optional[torch.Tensor], nbr: Optional[torch.Tensor], n_out: int, dy: torch.Tensor,
                K: int) -> torch.Tensor:
-    """dW [K, Cin, Cout] = sum over live pairs (i = nbr[k][o], o) of cat(x0, x1)[i]^T dy[o]; nbr None = pointwise (K = 1)."""
+    """dW [K, Cin, Cout] = sum over live pairs (i = nbr[k][o], o) of cat(x0, x1)[i]^T dy[o]; nbr None = pointwise (K = 1).
+    x0 / x1 / dy all float32 (st_sparse_conv_wgrad) or all float16 (st_sparse_conv_wgrad_h); dW float32, float32 sums, deterministic."""
     L = _lib.lib()
+    if x0.dtype not in (torch.float32, torch.float16) or dy.dtype != x0.dtype or (x1 is not None and x1.dtype != x0.dtype):
+        raise ValueError("conv_wgrad takes features and gradients that are all float32 or all float16")
+    ws_bytes, run = ((L.st_sparse_conv_wgrad_workspace_bytes, L.st_sparse_conv_wgrad) if x0.dtype == torch.float32 else
+                     (L.st_sparse_conv_wgrad_h_workspace_bytes, L.st_sparse_conv_wgrad_h))
     x0 = x0.contiguous()
     x1 = x1.contiguous() if x1 is not None else None
     dy = dy.contiguous()
@@ -36,29 +43,9 @@ def conv_wgrad(x0: torch.Tensor, x1: Optional[torch.Tensor], nbr: Optional[torch
     cout = dy.shape[1]
     nbr_ptr, nbr_stride = ops._nbr_args(nbr)
     dw = torch.empty((K, cin, cout), dtype=torch.float32, device=x0.device)
-    ws = _lib.workspace(L.st_sparse_conv_wgrad_workspace_bytes(K, cin, cout, n_out), x0.device)
-    _lib.check(L.st_sparse_conv_wgrad(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, nbr_stride, _lib.ptr(dy), cout,
-                                      _lib.ptr(dw), _lib.ptr(ws), ws.numel(), _lib.stream(x0.device)))
-    return dw
-
-
-def conv_wgrad_half(x0: torch.Tensor, x1: Optional[torch.Tensor], nbr: Optional[torch.Tensor], n_out: int, dy: torch.Tensor,
-                    K: int) -> torch.Tensor:
-    """`conv_wgrad` for float16 x0 / x1 / dy (st_sparse_conv_wgrad_h): dW [K, Cin, Cout] float32, float32 sums, deterministic."""
-    L = _lib.lib()
-    x0 = x0.contiguous()
-    x1 = x1.contiguous() if x1 is not None else None
-    dy = dy.contiguous()
-    if x0.dtype != torch.float16 or dy.dtype != torch.float16 or (x1 is not None and x1.dtype != torch.float16):
-        raise ValueError("conv_wgrad_half takes float16 features and gradients")
-    c0 = x0.shape[1]
-    cin = c0 + (x1.shape[1] if x1 is not None else 0)
-    cout = dy.shape[1]
-    nbr_ptr, nbr_stride = ops._nbr_args(nbr)
-    dw = torch.empty((K, cin, cout), dtype=torch.float32, device=x0.device)
-    ws = _lib.workspace(L.st_sparse_conv_wgrad_h_workspace_bytes(K, cin, cout, n_out), x0.device)
-    _lib.check(L.st_sparse_conv_wgrad_h(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, nbr_stride, _lib.ptr(dy), cout,
-                                        _lib.ptr(dw), _lib.ptr(ws), ws.numel(), _lib.stream(x0.device)))
+    ws = _lib.workspace(ws_bytes(K, cin, cout, n_out), x0.device)
+    _lib.check(run(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, nbr_stride, _lib.ptr(dy), cout, _lib.ptr(dw), _lib.ptr(ws),
+                   ws.numel(), _lib.stream(x0.device)))
     return dw
 
 
@@ -94,52 +81,25 @@ class SparseConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, x1, w, nbr, n_out, nbr_t, flip):
         ctx.half = half_path(x0)
-        if ctx.half:
-            ctx.dtypes = (x0.dtype, x1.dtype if x1 is not None else None, w.dtype)
-            x0 = x0.detach().to(torch.float16).contiguous()
-            x1 = x1.detach().to(torch.float16).contiguous() if x1 is not None else None
-            w_h = w.detach().to(torch.float16).contiguous()
-            y = ops.sparse_conv_half(x0, w_h, nbr, int(n_out), x1=x1)
-            ctx.save_for_backward(x0, x1, w_h)
-            ctx.nbr, ctx.nbr_t, ctx.flip, ctx.n_out = nbr, nbr_t, flip, int(n_out)
-            return y
-        x0 = x0.contiguous()
-        x1 = x1.contiguous() if x1 is not None else None
-        w_d = w.detach().contiguous()
-        y = ops.sparse_conv(x0, w_d, nbr, int(n_out), x1=x1)
-        ctx.save_for_backward(x0, x1, w_d)
+        ctx.dtypes = (x0.dtype, x1.dtype if x1 is not None else None, w.dtype)
+        storage = torch.float16 if ctx.half else x0.dtype  # (.to(storage) returns the same tensor on the float32 path)
+        x0 = x0.detach().to(storage).contiguous()
+        x1 = x1.detach().to(storage).contiguous() if x1 is not None else None
+        w = w.detach().to(storage).contiguous()
+        y = (ops.sparse_conv_half if ctx.half else ops.sparse_conv)(x0, w, nbr, int(n_out), x1=x1)
+        ctx.save_for_backward(x0, x1, w)
         ctx.nbr, ctx.nbr_t, ctx.flip, ctx.n_out = nbr, nbr_t, flip, int(n_out)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.half:
-            return SparseConvFn._backward_half(ctx, dy)
-        x0, x1, w = ctx.saved_tensors
-        dy = dy.contiguous()
+        x0, x1, w = ctx.saved_tensors  # in the storage dtype
+        dy = dy.to(w.dtype).contiguous()
         K = w.shape[0]
         dx0 = dx1 = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             wt = (w.flip(0) if ctx.flip else w).transpose(1, 2).contiguous()  # [K, Cout, Cin]
-            dx = ops.sparse_conv(dy, wt, ctx.nbr_t, x0.shape[0])
-            if x1 is None:
-                dx0 = dx
-            else:
-                c0 = x0.shape[1]
-                dx0, dx1 = dx[:, :c0].contiguous(), dx[:, c0:].contiguous()
-        if ctx.needs_input_grad[2]:
-            dw = conv_wgrad(x0, x1, ctx.nbr, ctx.n_out, dy, K)
-        return dx0, dx1, dw, None, None, None, None
-
-    @staticmethod
-    def _backward_half(ctx, dy):
-        x0, x1, w = ctx.saved_tensors  # float16
-        dy = dy.to(torch.float16).contiguous()
-        K = w.shape[0]
-        dx0 = dx1 = dw = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            wt = (w.flip(0) if ctx.flip else w).transpose(1, 2).contiguous()  # [K, Cout, Cin] half
-            dx = ops.sparse_conv_half(dy, wt, ctx.nbr_t, x0.shape[0])
+            dx = (ops.sparse_conv_half if ctx.half else ops.sparse_conv)(dy, wt, ctx.nbr_t, x0.shape[0])
             if x1 is None:
                 dx0 = dx
             else:
@@ -148,7 +108,7 @@ class SparseConvFn(torch.autograd.Function):
             dx0 = dx0.to(ctx.dtypes[0])
             dx1 = dx1.to(ctx.dtypes[1]) if dx1 is not None else None
         if ctx.needs_input_grad[2]:
-            dw = conv_wgrad_half(x0, x1, ctx.nbr, ctx.n_out, dy, K).to(ctx.dtypes[2])  # float32 for a float32 weight
+            dw = conv_wgrad(x0, x1, ctx.nbr, ctx.n_out, dy, K).to(ctx.dtypes[2])  # float32 for a float32 weight
         return dx0, dx1, dw, None, None, None, None
 
 
@@ -165,18 +125,11 @@ class MoveRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, order, scatter):
         ctx.order, ctx.scatter = order, bool(scatter)
-        return _move(x, order, scatter)
+        return ops.move_rows(x, order, scatter=scatter)
 
     @staticmethod
     def backward(ctx, g):
-        return _move(g.contiguous(), ctx.order, not ctx.scatter), None, None
-
-
-def _move(x, order, scatter):
-    """float16 rows (any width) through st_move_rows_h, 4-byte rows through st_move_rows."""
-    if x.dtype == torch.float16:
-        return ops.move_rows_half(x, order, scatter=scatter)
-    return ops.move_rows(x, order, scatter=scatter)
+        return ops.move_rows(g.contiguous(), ctx.order, not ctx.scatter), None, None
 
 
 def move_rows(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> torch.Tensor:

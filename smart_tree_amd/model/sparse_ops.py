@@ -204,24 +204,15 @@ def spatial_order(coords: torch.Tensor) -> torch.Tensor:
 
 
 def move_rows(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> torch.Tensor:
-    """x[order] (gather) or the inverse (out[order] = x, scatter) for a [N, C] tensor of 4-byte elements, order int32 [N]."""
+    """x[order] (gather) or the inverse (out[order] = x, scatter) for a [N, C] tensor, order int32 [N]: 4-byte elements through
+    st_move_rows, 2-byte elements (any C) through st_move_rows_h."""
     L = _lib.lib()
     x = x.contiguous()
-    assert x.element_size() == 4 and x.ndim == 2 and order.dtype == torch.int32
+    assert x.element_size() in (4, 2) and x.ndim == 2 and order.dtype == torch.int32
     out = torch.empty_like(x)
-    _lib.check(L.st_move_rows(_lib.ptr(x), x.shape[1], _lib.ptr(order), x.shape[0], _lib.ptr(out), int(scatter), _lib.stream(x.device)))
-    return out
-
-
-def move_rows_half(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> torch.Tensor:
-    """`move_rows` for a float16 [N, C] tensor, any C (st_move_rows_h)."""
-    L = _lib.lib()
-    x = x.contiguous()
-    assert x.dtype == torch.float16 and x.ndim == 2 and order.dtype == torch.int32
-    out = torch.empty_like(x)
-    if x.shape[1]:
-        _lib.check(L.st_move_rows_h(_lib.ptr(x), x.shape[1], _lib.ptr(order), x.shape[0], _lib.ptr(out), int(scatter),
-                                    _lib.stream(x.device)))
+    move = L.st_move_rows if x.element_size() == 4 else L.st_move_rows_h
+    if x.element_size() == 4 or x.shape[1]:
+        _lib.check(move(_lib.ptr(x), x.shape[1], _lib.ptr(order), x.shape[0], _lib.ptr(out), int(scatter), _lib.stream(x.device)))
     return out
 
 

@@ -176,3 +176,22 @@ def test_wgrad_chunked_rows(backend):
     ref = (x.double().T @ dy.double()).cpu()
     bound = (x.abs().double().T @ dy.abs().double()).cpu()
     _check(dw[0], ref, bound, "dW")
+
+
+def test_wgrad_workspace_chunk_policy(backend):
+    """The workspace queries are the outside view of the per-type row chunking (up to 64 chunks per offset for float32, 256 for half,
+    256-row steps): K = 1, cin = 4, cout = 3 gives nchunks * 48 + 256 bytes."""
+    L = _lib.lib()
+    f32, f16 = L.st_sparse_conv_wgrad_workspace_bytes, L.st_sparse_conv_wgrad_h_workspace_bytes
+    for n_out, want32, want16 in ((0, 304, 304), (256 * 64, 3328, 3328), (256 * 64 + 1, 33 * 48 + 256, 65 * 48 + 256)):
+        assert (f32(1, 4, 3, n_out), f16(1, 4, 3, n_out)) == (want32, want16), n_out
+    assert (33 * 48 + 256, 65 * 48 + 256) == (1840, 3376)
+    for bad in ((0, 4, 3, 10), (1, 0, 3, 10), (1, 4, 0, 10), (1, 4, 3, -1)):
+        assert f32(*bad) == -1 and f16(*bad) == -1, bad
+
+
+def test_conv_wgrad_refuses_mixed_dtypes(backend):
+    x, dy = torch.zeros(4, 8, device=backend), torch.zeros(4, 8, device=backend)
+    for a, b, c in ((x.half(), None, dy), (x, None, dy.half()), (x, x.half(), dy), (x.double(), None, dy.double())):
+        with pytest.raises(ValueError):
+            sg.conv_wgrad(a, b, None, 4, c, 1)

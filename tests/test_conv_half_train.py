@@ -1,6 +1,6 @@
-"""Half-precision sparse-convolution training kernels (csrc/sparse_conv_half.hip): st_sparse_conv_h_fwd (forward, and the data gradient
-over the transposed table), st_sparse_conv_wgrad_h and st_move_rows_h, through model/sparse_grad.py, on the CPU sanitizer build and on
-the GPU.
+"""Half-precision sparse-convolution training kernels: st_sparse_conv_h_fwd (forward, and the data gradient over the transposed table)
+and st_move_rows_h (csrc/sparse_conv_half.hip), st_sparse_conv_wgrad_h (the half policy of csrc/sparse_conv_grad.hip), through
+model/sparse_grad.py, on the CPU sanitizer build and on the GPU.
 
 * Small-integer data: every product and partial sum is exact in float32, so the forward and the data gradient must equal the float64
   contraction rounded once to half, and the weight gradient the float64 one, bit for bit.
@@ -18,7 +18,8 @@ from smart_tree_amd.model import sparse_grad as sg
 from smart_tree_amd.model import sparse_ops as ops
 from test_conv_grad import _coords, _table
 
-SRC = Path(__file__).resolve().parents[1] / "smart_tree_amd" / "csrc" / "sparse_conv_half.hip"
+CSRC = Path(__file__).resolve().parents[1] / "smart_tree_amd" / "csrc"
+SRC = {"HF_MFMA_CASE": CSRC / "sparse_conv_half.hip", "HF_VEC_CASE": CSRC / "sparse_conv_half.hip", "HW_FORM_CASE": CSRC / "sparse_conv_grad.hip"}
 U = 32 * 2.0 ** -24  # accumulation bound per unit of sum |a| |b|
 
 
@@ -109,11 +110,11 @@ def test_half_conv_grad_exact(backend, kind, cin, cout, c0):
 
 
 def test_every_dispatched_instance_has_a_case():
-    """Each instance the dispatch macros of sparse_conv_half.hip name is reached by a case of SHAPES (forward or its transpose)."""
-    text = SRC.read_text()
+    """Each instance the dispatch macros of sparse_conv_half.hip (forward) and sparse_conv_grad.hip (weight gradient) name is reached by
+    a case of SHAPES (forward or its transpose)."""
     named = set()
     for macro in ("HF_MFMA_CASE", "HF_VEC_CASE", "HW_FORM_CASE"):
-        for arg in re.findall(rf"^\s*{macro}\((\w+)\)\s*$", text, re.M):
+        for arg in re.findall(rf"^\s*{macro}\((\w+)\)\s*$", SRC[macro].read_text(), re.M):
             named.add((macro, arg))
     assert len(named) == 8, named
     reached = set()
@@ -185,8 +186,8 @@ def test_half_edge_cases(backend, K):
         x, w, dy = _int_data(n, cin, cout, n, K, seed=K + cin)
         y0 = ops.sparse_conv_half(x.to(backend), w.half().to(backend), nbr, n).cpu()
         yv = ops.sparse_conv_half(x.to(backend), w.half().to(backend), view, n).cpu()
-        dw0 = sg.conv_wgrad_half(x.to(backend), None, nbr, n, dy.to(backend), K).cpu()
-        dwv = sg.conv_wgrad_half(x.to(backend), None, view, n, dy.to(backend), K).cpu()
+        dw0 = sg.conv_wgrad(x.to(backend), None, nbr, n, dy.to(backend), K).cpu()
+        dwv = sg.conv_wgrad(x.to(backend), None, view, n, dy.to(backend), K).cpu()
         y64, dx64, dw64, *_ = _oracle64(x, w, nbr, n, dy)
         assert _bits_equal(y0, y64.half()) and _bits_equal(yv, y0)
         assert torch.equal(dw0.double(), dw64) and torch.equal(dwv, dw0)
@@ -197,7 +198,7 @@ def test_half_edge_cases(backend, K):
     empty = torch.zeros((K, 0), dtype=torch.int32, device=backend)
     x = torch.ones(5, 16, dtype=torch.float16, device=backend)
     assert ops.sparse_conv_half(x, torch.ones(K, 16, 16, dtype=torch.float16, device=backend), empty, 0).shape == (0, 16)
-    dw = sg.conv_wgrad_half(x, None, empty, 0, torch.zeros((0, 16), dtype=torch.float16, device=backend), K)
+    dw = sg.conv_wgrad(x, None, empty, 0, torch.zeros((0, 16), dtype=torch.float16, device=backend), K)
     assert dw.shape == (K, 16, 16) and dw.dtype == torch.float32 and not dw.any()
 
 
@@ -208,8 +209,25 @@ def test_half_wgrad_chunked_rows(backend):
         g = torch.Generator().manual_seed(cin)
         x = torch.randint(-2, 3, (n, cin), generator=g).half()
         dy = torch.randint(-2, 3, (n, cout), generator=g).half()
-        dw = sg.conv_wgrad_half(x.to(backend), None, None, n, dy.to(backend), 1).cpu()
+        dw = sg.conv_wgrad(x.to(backend), None, None, n, dy.to(backend), 1).cpu()
         assert torch.equal(dw[0].double(), x.double().T @ dy.double())
+
+
+@pytest.mark.parametrize("kind,cin,cout,c0", [("subm", 8, 8, 8), ("down", 8, 16, 8), ("up", 16, 8, 16), ("point", 3, 8, 3),
+                                              ("subm", 12, 6, 6), ("point", 6, 5, 6)])
+def test_half_vector_wgrad_equals_float32_kernel(backend, kind, cin, cout, c0):
+    """The vector form on half inputs gives the bits of the float32 kernel on the same values: the conversions are exact, both run one
+    body with the same batches (cin4 + cout4 <= 32: 256 pairs per batch in either type) and the same chunks (n_out <= 16384).  Shapes
+    with cin >= 16 and cout >= 16 take the matrix form and are not expected to."""
+    nbr, n_in, n_out, _, _ = _table(kind, backend)
+    K = 1 if nbr is None else 27
+    g = torch.Generator().manual_seed(31 + 7 * cin + cout)
+    x = torch.randn(n_in, cin, generator=g).half().to(backend)
+    dy = torch.randn(n_out, cout, generator=g).half().to(backend)
+    x0, x1 = x[:, :c0].contiguous(), (x[:, c0:].contiguous() if c0 < cin else None)
+    dw_h = sg.conv_wgrad(x0, x1, nbr, n_out, dy, K)
+    dw_f = sg.conv_wgrad(x0.float(), x1.float() if x1 is not None else None, nbr, n_out, dy.float(), K)
+    assert dw_h.dtype == torch.float32 and torch.equal(dw_h, dw_f)
 
 
 @pytest.mark.parametrize("kind,cin,cout,c0", [("subm", 8, 8, 8), ("subm", 32, 16, 16), ("down", 16, 32, 16), ("up", 32, 16, 32),

@@ -31,7 +31,8 @@ extern "C" {
  * 105: st_centre_cloud_box_seg and st_voxelize_blocks_box_seg added (no existing signature or st_abi_entries value changed);
  * st_component_csr_knn_workspace_bytes asks for one more int32 per table entry.
  * 107: st_synth_points_seg and st_synth_philox added (no existing signature changed).
- * 108: st_prediction_metrics and its three size queries added (no existing signature changed). */
+ * 108: st_prediction_metrics and its three size queries added (no existing signature changed).
+ * 109: the st_render_* calls added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -470,6 +471,52 @@ int st_prediction_metrics(const float* radius, const float* direction, const flo
                           const int64_t* seg_off_host, int n_seg, int vector_class, int target_radius_log,
                           const float* thr_host, int n_thr, const float* edges_host, int n_edges,
                           int64_t* tally_ints, double* tally_sums, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- rendering: clouds and skeletons to images (csrc/render.hip) -------------------------------------------
+ * replaces: o3d_abstractions/camera.py:71-101 (Renderer.capture: open3d's OffscreenRenderer) and the to_o3d_* geometry built for
+ *           it (model/render.py:7-35).  A frame is: st_render_clear, any number of st_render_points / st_render_segments calls (each
+ *           with its own id range, in the order of the frame's items), st_render_resolve.  All of them take the SAME workspace of
+ *           st_render_workspace_bytes(V, H, W) bytes: it holds the framebuffer [V,H,W] of 64-bit keys = (bits of the positive
+ *           float32 depth) << 32 | id, min-reduced with one atomic per covered pixel -- the nearest surface wins, equal depths go
+ *           to the lowest id, and the result does not depend on the order of arrival (bit-identical from call to call).
+ * cams [V,16] float32 DEVICE: R (9, row-major), t (3), fx, fy, cx, cy.  Camera space is R p + t, +z forward; pixel (column u, row v)
+ *   has its centre at the integer (u, v).  The float32 operation order is the header comment of csrc/render.hip.
+ * st_render_points: xyz [n,3], radius [n] world radii or NULL.  A point goes to its nearest pixel and covers the disc of
+ *   max(point_px/2, fx r / z) pixels around its projection (point_px = 1: exactly one pixel); depth z.  Culled: z <= near,
+ *   non-finite coordinates, off the viewport.  Ids id_base + i.
+ * st_render_segments: a, b [m,3], r1, r2 [m]: screen-space capsules between the projected ends (clipped at z = near, radius
+ *   interpolated) with pixel radii max(fx r / z, min_px/2), depth of a sphere impostor around the perspective-correct axis point,
+ *   never below near.  Skeleton tubes, and with radius 0 and min_px = 1 lines one pixel wide.  Ids id_base + i.
+ * st_render_resolve: rgb uint8 [V,H,W,3], depth float32 [V,H,W] (+inf on the background), ids int32 [V,H,W] (-1); each may be NULL.
+ *   items_host [n_items] (HOST; it travels as a kernel argument) says who owns the ids, in order, and how they are coloured -- the
+ *   colour is looked up per visible pixel.  An id no item owns is black.  edl_strength > 0: eye-dome shading from the depths of the
+ *   4 neighbours at edl_px.  Background is white.
+ * Refused, nothing launched: V < 1 or > 65536, W or H < 1 or > 16384, a null input with a count above 0, null cameras, ids that
+ *   reach 2^31, near / point_px / min_px / edl_strength negative or not finite (near must be > 0), more than 16 items, a class
+ *   item without a colour map, a workspace below st_render_workspace_bytes (-1 for a refused view).  No write happens outside the
+ *   three images and the workspace, whatever the coordinates. */
+#define ST_RENDER_UNIFORM 0 /* rgb */
+#define ST_RENDER_RGB 1     /* data: float32 [count,3] */
+#define ST_RENDER_CLASS 2   /* data: int32 [count], cmap: float32 [n_classes,3]; a class outside [0, n_classes) is black */
+#define ST_RENDER_SCALAR 3  /* data: float32 [count] through the blue-cyan-green-yellow-red ramp over [lo, hi] */
+#define ST_RENDER_ID 4      /* data: int32 [count] through a hash (branch ids) */
+typedef struct StRenderItem {
+    int64_t count; /* ids owned by the item: points or segments drawn for it */
+    int32_t mode, n_classes;
+    const void* data;  /* DEVICE */
+    const float* cmap; /* DEVICE */
+    float lo, hi;
+    float rgb[3];
+    float reserved;
+} StRenderItem;
+int64_t st_render_workspace_bytes(int V, int H, int W);
+int st_render_clear(int V, int H, int W, void* ws, int64_t ws_bytes, void* stream);
+int st_render_points(const float* xyz, const float* radius, int64_t n, int64_t id_base, float point_px, const float* cams, int V,
+                     int H, int W, float near, void* ws, int64_t ws_bytes, void* stream);
+int st_render_segments(const float* a, const float* b, const float* r1, const float* r2, int64_t m, int64_t id_base, float min_px,
+                       const float* cams, int V, int H, int W, float near, void* ws, int64_t ws_bytes, void* stream);
+int st_render_resolve(const StRenderItem* items_host, int n_items, int V, int H, int W, float edl_strength, int edl_px,
+                      uint8_t* rgb, float* depth, int32_t* ids, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

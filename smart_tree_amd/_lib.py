@@ -81,6 +81,11 @@ SIGNATURES = {
     "st_prediction_metrics_tally_sums": (I64, [c_int]),
     "st_prediction_metrics_workspace_bytes": (I64, [I64, c_int, c_int]),
     "st_prediction_metrics": (c_int, [P, P, P, c_int, P, c_int, P, I64, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P, I64, P]),
+    "st_render_workspace_bytes": (I64, [c_int, c_int, c_int]),
+    "st_render_clear": (c_int, [c_int, c_int, c_int, P, I64, P]),
+    "st_render_points": (c_int, [P, P, I64, I64, c_float, P, c_int, c_int, c_int, c_float, P, I64, P]),
+    "st_render_segments": (c_int, [P, P, P, P, I64, I64, c_float, P, c_int, c_int, c_int, c_float, P, I64, P]),
+    "st_render_resolve": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_int, P, P, P, P, I64, P]),
     # batched forms (B clouds per launch set)
     "st_centre_cloud_seg": (c_int, [P, I64, P, c_int, P, P, I64, P]),
     "st_centre_cloud_box_seg": (c_int, [P, I64, P, c_int, P, P, I64, P, P]),
@@ -147,12 +152,19 @@ ENQUEUE_ONLY = frozenset({
     "st_sample_tubes_workspace_bytes", "st_sample_tubes_fill", "st_skeleton_match_workspace_bytes", "st_skeleton_match",
     "st_synth_points_seg", "st_synth_philox",
     "st_prediction_metrics_tally_ints", "st_prediction_metrics_tally_sums", "st_prediction_metrics_workspace_bytes", "st_prediction_metrics",
+    "st_render_workspace_bytes", "st_render_clear", "st_render_points", "st_render_segments", "st_render_resolve",
 })
 
 
 # Entry points that wait only when asked for a count on the host: `<name>_nowait` is the GIL-keeping binding for calls
 # that pass NULL for it (st_make_edges: n_edges_host, st_assemble_branches: counts_host).
 NOWAIT_VARIANTS = ("st_make_edges", "st_assemble_branches", "st_make_edges_seg")
+
+
+class StRenderItem(ctypes.Structure):
+    """One item of a frame for st_render_resolve (include/smarttree_hip.h)."""
+    _fields_ = [("count", c_int64), ("mode", ctypes.c_int32), ("n_classes", ctypes.c_int32), ("data", c_void_p), ("cmap", c_void_p),
+                ("lo", c_float), ("hi", c_float), ("rgb", c_float * 3), ("reserved", c_float)]
 
 
 class _Bound:

@@ -287,6 +287,13 @@ def _capture(run_dir: Path, epoch: int, loaders: dict, model, cfg, device, group
         out.mkdir(parents=True, exist_ok=True)
         for cloud in capture_clouds(loader, model, cfg["cmap"], fp16=cfg["fp16"], device=device):
             save_cloud(out / f"{Path(cloud.filename).stem}.npz", cloud)
+            if cfg.get("capture_images", False):  # the reference's render_cloud pictures, beside the .npz
+                from ..render import Renderer
+                from .render import write_cloud_images
+
+                size = cfg.get("capture_image_size", [960, 540])
+                write_cloud_images(Renderer(int(size[0]), int(size[1])), cloud.to_device(device), out / Path(cloud.filename).stem,
+                                   cmap=cfg["cmap"])
 
 
 def _gather_rng(group) -> list:

@@ -2,7 +2,9 @@
 
 Constructor keywords, defaults and `process_cloud(path=None, cloud=None)` / `post_process(skeleton)`
 match the reference.  Additive change: `process_cloud` returns the `DisjointTreeSkeleton` (the
-reference only views / saves it).  Viewing needs open3d and is out of scope; `save_outputs` writes
+reference only views / saves it).  An interactive window needs open3d and is out of scope: with a view flag
+set and `view_path` given, the views are rendered offscreen (smart_tree_amd/render.py) and written there as
+`model_output.png` / `skeleton.png`; without `view_path` a view flag raises.  `save_outputs` writes
 dependency-free files (util/file.py).
 """
 from __future__ import annotations
@@ -23,7 +25,7 @@ class Pipeline:
     def __init__(self, preprocessing, model_inference, skeletonizer, repair_skeletons=False, smooth_skeletons=False,
                  smooth_kernel_size=0, prune_skeletons=False, min_skeleton_radius=0.0, min_skeleton_length=1000,
                  view_model_output=False, view_skeletons=False, save_outputs=False, save_path="/", branch_classes=[0],
-                 cmap=[[1, 0, 0], [0, 1, 0]], device=torch.device("cuda:0")):
+                 cmap=[[1, 0, 0], [0, 1, 0]], device=torch.device("cuda:0"), view_path=None):
         self.preprocessing = preprocessing
         self.model_inference = model_inference
         self.skeletonizer = skeletonizer
@@ -40,6 +42,7 @@ class Pipeline:
         self.branch_classes = branch_classes
         self.cmap = np.asarray(cmap)
         self.device = torch.device(device)
+        self.view_path = view_path
         self.last_labelled_cloud = None
 
     def process_cloud(self, path: Path = None, cloud: Cloud = None) -> DisjointTreeSkeleton:
@@ -56,7 +59,9 @@ class Pipeline:
             self.post_process(skeleton)
             skeleton.skeletons  # materialise: device post-processing kernel, one D->H copy, BranchSkeleton objects
         if self.view_model_output or self.view_skeletons:
-            raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")
+            if self.view_path is None:
+                raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")
+            self.write_views(Path(self.view_path), lc, skeleton)
         if self.save_outputs:  # reference pipeline.py:85-93 (skeleton.ply / cloud.ply; meshes need open3d)
             sp = Path(self.save_path)
             save_skeleton_npz(sp / "skeleton.npz", skeleton)
@@ -94,8 +99,24 @@ class Pipeline:
         if len(parts) != len(clouds):
             raise RuntimeError(f"process_clouds: {len(parts)} skeleton(s) for a batch of {len(clouds)} clouds")
         if self.view_model_output or self.view_skeletons:
-            raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")
+            if self.view_path is None:
+                raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")
+            for k, (cloud_k, part) in enumerate(zip(lc.split(), parts)):
+                self.write_views(Path(self.view_path), cloud_k, part, prefix=f"cloud_{k}_")
         return parts
+
+    def write_views(self, path: Path, labelled_cloud: Cloud, skeleton, prefix: str = "", width: int = 1920, height: int = 1080) -> None:
+        """What the reference shows in a window, as pictures: `model_output.png` (the segmentation; view_model_output) and
+        `skeleton.png` (the tubes coloured by branch over the cloud in its own colours; view_skeletons)."""
+        from .render import Renderer, cloud_items, fit, skeleton_items, write_png
+
+        r = Renderer(width, height)
+        look = lambda items: r.render(items, [fit(items, (-1, 0, 0), width, height)], outputs=("rgb",))["rgb"][0]
+        if self.view_model_output:
+            write_png(path / f"{prefix}model_output.png", look(cloud_items(labelled_cloud, "class", cmap=self.cmap)))
+        if self.view_skeletons:
+            items = cloud_items(labelled_cloud, "rgb") + skeleton_items(skeleton, device=self.device)
+            write_png(path / f"{prefix}skeleton.png", look(items))
 
     def post_process(self, skeleton: DisjointTreeSkeleton) -> None:
         if self.prune_skeletons:

@@ -188,7 +188,9 @@ int st_component_csr(const int64_t* edges, const float* w, int64_t E, const int3
                      uint32_t* col, float* wgt, void* ws, int64_t ws_bytes, void* stream);
 int64_t st_skeleton_workspace_bytes(int64_t m, int64_t n_comp);
 /* stats_host: optional, 16 x int64 (see csrc/skeleton.hip): [0] SSSP rounds .. [6] = branches of the cloud | path vertices << 32
- * (sample_tree stage), [7] in: time the select launches, [8] helper workgroups were lost (fall-back ran), [9] helper workgroups launched.
+ * (sample_tree stage), [7] in: time the select launches, [8] helper workgroups were lost (fall-back ran), [9] helper workgroups launched,
+ * [10] form of the SSSP that produced dist: 0 a launch per round, 1 the persistent launch completed, 2 it gave up at a barrier and
+ * the rounds were redone by launches.
  * comp_size_host is unused and may be NULL (the claim grid is laid out on the device from comp_off); grid_cell < 0:
  * cell = max(max(rad) / -grid_cell, 1e-4) with the maximum reduced on the device -- neither costs the caller a read-back */
 int st_skeleton_components(int n_comp, const int32_t* comp_off, const int32_t* comp_size_host, int64_t m, const float* pts,

@@ -129,6 +129,8 @@ struct SkArgs {
 template <class T>
 __device__ __forceinline__ T ld(const T* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float ld(const float* p) { return __uint_as_float(ld((const unsigned*)p)); }
+template <class T>
+__device__ __forceinline__ void st(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // workgroup-scope load: may be served by this CU's L1 / this XCD's L2
 __device__ __forceinline__ unsigned ld_wg(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ int ld_wg(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -179,19 +181,22 @@ __device__ __forceinline__ float sk_dist(const float* a, const float* b) {
 // filled with SK_Q_HOLE, which readers skip.  A frontier is read as the concatenation shard 0 .. SK_FS-1, overflow.
 #define SK_FS 16
 #define SK_Q_HOLE 0xffffffffu
+// The SSSP rounds exist in two forms: a launch per round (k_sk_sssp_round) and every round in one persistent launch
+// (k_sk_sssp_coop); both run the one body below (sk_sssp_one_round<COOP>).  What ANOTHER workgroup may have written -- the
+// frontier counters, the queue entries and holes, the distances -- was written by an earlier launch in the first form (a
+// plain access sees it) and earlier in the SAME launch in the second, where only an agent-scope access does (the L2s of
+// the eight XCDs are not coherent with each other for plain accesses).  These two accessors are that whole difference.
+template <bool COOP>
+__device__ __forceinline__ unsigned sk_xld(const unsigned* p) { if constexpr (COOP) return ld(p); else return *p; }
+template <bool COOP>
+__device__ __forceinline__ void sk_xst(unsigned* p, unsigned v) { if constexpr (COOP) st(p, v); else *p = v; }
+
 // where `n` entries of workgroup-shard `shard` go in queue `q`; fc = the generation's SK_FS + 1 counters
+template <bool COOP>
 __device__ __forceinline__ unsigned sk_q_reserve(unsigned* q, unsigned* fc, unsigned seg, unsigned shard, unsigned n) {
     const unsigned at = atomicAdd(&fc[shard], n);
     if (at + n <= seg) return shard * seg + at;
-    for (unsigned i = at; i < seg; i++) q[shard * seg + i] = SK_Q_HOLE;  // (at most n - 1 slots, once per shard and launch)
-    return SK_FS * seg + atomicAdd(&fc[SK_FS], n);
-}
-
-// the same for the persistent form: the holes are written where another workgroup's agent-scope read finds them
-__device__ __forceinline__ unsigned sk_q_reserve_coop(unsigned* q, unsigned* fc, unsigned seg, unsigned shard, unsigned n) {
-    const unsigned at = atomicAdd(&fc[shard], n);
-    if (at + n <= seg) return shard * seg + at;
-    for (unsigned i = at; i < seg; i++) __hip_atomic_store(&q[shard * seg + i], SK_Q_HOLE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (unsigned i = at; i < seg; i++) sk_xst<COOP>(&q[shard * seg + i], SK_Q_HOLE);  // (at most n - 1 slots, once per shard and round)
     return SK_FS * seg + atomicAdd(&fc[SK_FS], n);
 }
 
@@ -229,26 +234,29 @@ __global__ void __launch_bounds__(1024) k_sk_fill_comp_of(SkArgs A) {
 }
 
 // ------------------------------------------------------------------------------------ SSSP ---
-// Launch r: global frontier r%2 -> (r+1)%2; counts rotate through cnt[0..2].  The frontier of a tree-shaped graph
-// is small (a few hundred vertices) and hundreds of levels deep, so a launch per level is bound by launch latency.
-// Each workgroup therefore keeps relaxing what IT improved for up to `hops` further levels from a queue in LDS
-// before handing the rest to the next launch.  The distances are the least fixed point of d[v] = min(d[u] + w)
+// Round r: global frontier r%2 -> (r+1)%2; counts rotate through the three generations of fcnt.  The frontier of a
+// tree-shaped graph is small (a few hundred vertices) and hundreds of levels deep, so a launch per level is bound by launch
+// latency.  Each workgroup therefore keeps relaxing what IT improved for up to `hops` further levels from a queue in LDS
+// before handing the rest to the next round.  The distances are the least fixed point of d[v] = min(d[u] + w)
 // whatever the order of relaxations (atomicMin; every improvement is queued again), so the result is the same
-// as one level per launch -- at 1/hops of the launches.
+// as one level per round -- at 1/hops of the rounds.  Returns false when the round's frontier is empty (the same for
+// every workgroup: the counters were final before the round began).  bdim = blockDim.x, read by the KERNEL: read in here, it
+// is no longer folded to the uniform workgroup size and becomes a vector load that every launch waits for at its head.
 #define SK_LQ 1024  // entries per local generation; overflow goes straight to the global queue
-__global__ void __launch_bounds__(SK_WIDE_BLOCK) k_sk_sssp_round(SkArgs A, int r, int hops, int glanes, int lcap) {
+template <bool COOP>
+__device__ __forceinline__ bool sk_sssp_one_round(const SkArgs& A, int r, int hops, int glanes, int lcap, unsigned bdim) {
     __shared__ unsigned lq[2][SK_LQ];
     __shared__ unsigned ln[3], lq_base;  // generation h fills lq[h & 1], counted by ln[h % 3]
-    __shared__ unsigned fpre[SK_FS + 2];  // this launch's frontier: entries in front of each shard / of the overflow area
+    __shared__ unsigned fpre[SK_FS + 2];  // this round's frontier: entries in front of each shard / of the overflow area
     const unsigned* fc_in = A.fcnt + (r % 3) * (SK_FS + 1);
     unsigned* fc_out = A.fcnt + ((r + 1) % 3) * (SK_FS + 1);
-    if (blockIdx.x == 0 && threadIdx.x <= SK_FS) A.fcnt[((r + 2) % 3) * (SK_FS + 1) + threadIdx.x] = 0u;
+    if (blockIdx.x == 0 && threadIdx.x <= SK_FS) sk_xst<COOP>(&A.fcnt[((r + 2) % 3) * (SK_FS + 1) + threadIdx.x], 0u);
     const unsigned seg = A.fseg, shard = blockIdx.x % SK_FS;
     if (threadIdx.x == 0) {
         unsigned run = 0;
         for (int s_ = 0; s_ <= SK_FS; s_++) {
             fpre[s_] = run;
-            const unsigned c_ = fc_in[s_];
+            const unsigned c_ = sk_xld<COOP>(&fc_in[s_]);
             run += s_ < SK_FS && c_ > seg ? seg : c_;  // a shard holds at most `seg` entries (the rest went to the overflow area)
         }
         fpre[SK_FS + 1] = run;
@@ -256,39 +264,40 @@ __global__ void __launch_bounds__(SK_WIDE_BLOCK) k_sk_sssp_round(SkArgs A, int r
     if (threadIdx.x < 3) ln[threadIdx.x] = 0;
     __syncthreads();
     const unsigned count = fpre[SK_FS + 1];
-    if (count == 0) return;  // (uniform)
+    if (count == 0) return false;  // (uniform)
     const unsigned* q = (r & 1) ? A.q1 : A.q0;
     unsigned* qn = (r & 1) ? A.q0 : A.q1;
     const bool lookfirst = lcap >= 0;
     if (lcap < 0) lcap = -lcap;
     const unsigned round = (unsigned)r + 1u;  // stamp[v] == round: v already sits in the next global frontier
     const int lane = threadIdx.x & (glanes - 1);  // `glanes` lanes share one vertex (rows hold ~16 edges)
-    const unsigned wave = threadIdx.x / glanes, nwv = blockDim.x / glanes;
+    const unsigned wave = threadIdx.x / glanes, nwv = bdim / glanes;
     const unsigned gw = blockIdx.x * nwv + wave, tw = gridDim.x * nwv;
-    // one lane group per vertex: relax its edges; improved neighbours go to the local generation `out`
-#define SK_RELAX(u, du, out, out_n)                                                                        \
-    {                                                                                                      \
-        const uint32_t s_ = A.row_off[u], e_ = A.row_off[(u) + 1];                                         \
-        for (uint32_t t = s_ + lane; t < e_; t += glanes) {                                                    \
-            const unsigned v = A.col[t];                                                                   \
-            const unsigned o = st_f2ord((du) + A.wgt[t]);                                                  \
-            if (lookfirst && o >= A.dist_ord[v]) continue; /* plain load: a stale line holds an OLDER, larger value */ \
-            const unsigned old = atomicMin(&A.dist_ord[v], o);                                             \
-            if (o < old) {                                                                                 \
-                const unsigned slot = atomicAdd(out_n, 1u);                                                \
-                if (slot < SK_LQ) (out)[slot] = v;                                                         \
-                else if (atomicExch(&A.stamp[v], round) != round) qn[sk_q_reserve(qn, fc_out, seg, shard, 1u)] = v; \
-            }                                                                                              \
-        }                                                                                                  \
-    }
+    // v joins the next global frontier (callers stamp it first: once per round)
+    auto push = [&](unsigned v) { sk_xst<COOP>(&qn[sk_q_reserve<COOP>(qn, fc_out, seg, shard, 1u)], v); };
+    // one lane group per vertex: relax its edges; improved neighbours go to local generation `g`
+    auto relax = [&](unsigned u, float du, int g) {
+        const uint32_t s_ = A.row_off[u], e_ = A.row_off[u + 1];
+        for (uint32_t t = s_ + lane; t < e_; t += glanes) {
+            const unsigned v = A.col[t];
+            const unsigned o = st_f2ord(du + A.wgt[t]);
+            if (lookfirst && o >= sk_xld<COOP>(&A.dist_ord[v])) continue;  // (a launch per round: a plain load -- a stale line holds an OLDER, larger value)
+            const unsigned old = atomicMin(&A.dist_ord[v], o);
+            if (o < old) {
+                const unsigned slot = atomicAdd(&ln[g % 3], 1u);
+                if (slot < SK_LQ) lq[g & 1][slot] = v;
+                else if (atomicExch(&A.stamp[v], round) != round) push(v);
+            }
+        }
+    };
     for (unsigned f = gw; f < count; f += tw) {
         int sh = 0;  // the f-th entry of the frontier sits in shard `sh` (SK_FS: the overflow area)
 #pragma unroll
         for (int s_ = 1; s_ <= SK_FS; s_++) sh = f >= fpre[s_] ? s_ : sh;
-        const unsigned u = q[(int64_t)sh * seg + (f - fpre[sh])];
+        const unsigned u = sk_xld<COOP>(&q[(int64_t)sh * seg + (f - fpre[sh])]);
         if (u == SK_Q_HOLE) continue;  // (wave-uniform: one vertex per lane group)
-        const float du = st_ord2f(A.dist_ord[u]);  // written before this launch
-        SK_RELAX(u, du, lq[0], &ln[0]);
+        const float du = st_ord2f(sk_xld<COOP>(&A.dist_ord[u]));  // written before this round
+        relax(u, du, 0);
     }
     int h = 1;  // generation being read: lq[(h - 1) & 1], ln[(h - 1) % 3]
     for (; h < hops; h++) {
@@ -298,23 +307,21 @@ __global__ void __launch_bounds__(SK_WIDE_BLOCK) k_sk_sssp_round(SkArgs A, int r
         if (ncur == 0) break;  // uniform
         if (threadIdx.x == 0) ln[(h + 1) % 3] = 0;  // counter of the generation after this one (last read two barriers ago)
         const unsigned* in = lq[(h - 1) & 1];
-        unsigned* out = lq[h & 1];
         if (ncur > (unsigned)lcap) {
-            // a launch lasts as long as its busiest workgroup: what exceeds `lcap` vertices per level goes back to the global
-            // frontier, where the next launch deals it out over all workgroups
-            for (unsigned i = lcap + threadIdx.x; i < ncur; i += blockDim.x) {
+            // a round lasts as long as its busiest workgroup: what exceeds `lcap` vertices per level goes back to the global
+            // frontier, where the next round deals it out over all workgroups
+            for (unsigned i = lcap + threadIdx.x; i < ncur; i += bdim) {
                 const unsigned v = in[i];
-                if (atomicExch(&A.stamp[v], round) != round) qn[sk_q_reserve(qn, fc_out, seg, shard, 1u)] = v;
+                if (atomicExch(&A.stamp[v], round) != round) push(v);
             }
             ncur = (unsigned)lcap;
         }
         for (unsigned i = wave; i < ncur; i += nwv) {
             const unsigned u = in[i];
             const float du = st_ord2f(ld(&A.dist_ord[u]));  // improved during this launch: read it where the atomics act
-            SK_RELAX(u, du, out, &ln[h % 3]);
+            relax(u, du, h);
         }
     }
-#undef SK_RELAX
     __syncthreads();
     // what is left joins the next global frontier (once per vertex: stamp)
     const unsigned have = ln[(h - 1) % 3];
@@ -324,32 +331,35 @@ __global__ void __launch_bounds__(SK_WIDE_BLOCK) k_sk_sssp_round(SkArgs A, int r
     unsigned* keep_n = &ln[h % 3];
     if (threadIdx.x == 0) *keep_n = 0;
     __syncthreads();
-    for (unsigned i = threadIdx.x; i < nrem; i += blockDim.x) {
+    for (unsigned i = threadIdx.x; i < nrem; i += bdim) {
         const unsigned v = rem[i];
         if (atomicExch(&A.stamp[v], round) != round) keep[atomicAdd(keep_n, 1u)] = v;
     }
     __syncthreads();
     const unsigned nloc = *keep_n;
-    if (threadIdx.x == 0 && nloc) lq_base = sk_q_reserve(qn, fc_out, seg, shard, nloc);
+    if (threadIdx.x == 0 && nloc) lq_base = sk_q_reserve<COOP>(qn, fc_out, seg, shard, nloc);
     __syncthreads();
-    for (unsigned i = threadIdx.x; i < nloc; i += blockDim.x) qn[lq_base + i] = keep[i];
+    for (unsigned i = threadIdx.x; i < nloc; i += bdim) sk_xst<COOP>(&qn[lq_base + i], keep[i]);
+    return true;
 }
 
+// one round per launch
+__global__ void __launch_bounds__(SK_WIDE_BLOCK) k_sk_sssp_round(SkArgs A, int r, int hops, int glanes, int lcap) {
+    (void)sk_sssp_one_round<false>(A, r, hops, glanes, lcap, blockDim.x);
+}
 
 // ---- the same rounds in ONE launch: a persistent grid with a barrier between the rounds -----------------------------------
 // A launch per round costs its launch latency ~100 times over (a 1M-point tree: 96 rounds of 22-39 us, most of it the
 // launch) and a host read-back per batch of rounds.  Here the workgroups stay: round r ends at a grid barrier (one arrival
 // per workgroup on its group's counter, the last of a group on the top counter, everybody polls the top counter), the
 // frontier counters tell every workgroup whether another round is due.  Everything that crosses workgroups inside the
-// launch -- distances, queue entries, counters -- is read and written at agent scope (the L2s of the eight XCDs are not
-// coherent with each other for plain accesses); the adjacency is read-only.  The grid must be resident as a whole: the host
-// launches at most SK_COOP_BLOCKS workgroups of 256 lanes (four per compute unit) and a workgroup that waits longer than
-// ~2 s at a barrier gives up and flags the launch (the host then falls back to a launch per round).
+// launch -- distances, queue entries, counters -- is read and written at agent scope (sk_xld / sk_xst above); the adjacency
+// is read-only.  The grid must be resident as a whole: the host launches at most SK_COOP_BLOCKS workgroups of 256 lanes
+// (four per compute unit) and a workgroup that waits longer than ~2 s at a barrier gives up and flags the launch (the host
+// then falls back to a launch per round).
 #define SK_COOP_BLOCKS 1024
 #define SK_COOP_GROUP 32
 #define SK_COOP_STRIDE 16  // words between the barrier counters (one 64-byte line each)
-__device__ __forceinline__ unsigned ld_u(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_u(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // bar[0] top counter, bar[SK_COOP_STRIDE * (1 + g)] counter of group g, bar[1] "gave up" flag.  Returns false on a time-out.
 __device__ __forceinline__ bool sk_grid_barrier(unsigned* bar, unsigned round) {
@@ -366,9 +376,9 @@ __device__ __forceinline__ bool sk_grid_barrier(unsigned* bar, unsigned round) {
         const unsigned want = ngroups * (round + 1u);
         int ok = 1;
         const long long t0 = wall_clock64();
-        while (ld_u(&bar[0]) < want) {
+        while (ld(&bar[0]) < want) {
             __builtin_amdgcn_s_sleep(2);
-            if (ld_u(&bar[1]) != 0u || wall_clock64() - t0 > 200000000ll) { st_u(&bar[1], 1u); ok = 0; break; }  // (100 MHz clock)
+            if (ld(&bar[1]) != 0u || wall_clock64() - t0 > 200000000ll) { st(&bar[1], 1u); ok = 0; break; }  // (100 MHz clock)
         }
         ok_ = ok;
     }
@@ -377,104 +387,11 @@ __device__ __forceinline__ bool sk_grid_barrier(unsigned* bar, unsigned round) {
 }
 
 __global__ void __launch_bounds__(SK_WIDE_BLOCK) k_sk_sssp_coop(SkArgs A, int hops, int glanes, int lcap, unsigned* bar, int max_rounds) {
-    __shared__ unsigned lq[2][SK_LQ];
-    __shared__ unsigned ln[3], lq_base;
-    __shared__ unsigned fpre[SK_FS + 2];
-    const unsigned seg = A.fseg, shard = blockIdx.x % SK_FS;
-    const bool lookfirst = lcap >= 0;
-    if (lcap < 0) lcap = -lcap;
-    const int lane = threadIdx.x & (glanes - 1);
-    const unsigned wave = threadIdx.x / glanes, nwv = blockDim.x / glanes;
-    const unsigned gw = blockIdx.x * nwv + wave, tw = gridDim.x * nwv;
     for (int r = 0; r < max_rounds; r++) {
-        const unsigned* fc_in = A.fcnt + (r % 3) * (SK_FS + 1);
-        unsigned* fc_out = A.fcnt + ((r + 1) % 3) * (SK_FS + 1);
-        if (blockIdx.x == 0 && threadIdx.x <= SK_FS) st_u(&A.fcnt[((r + 2) % 3) * (SK_FS + 1) + threadIdx.x], 0u);
-        if (threadIdx.x == 0) {
-            unsigned run = 0;
-            for (int s_ = 0; s_ <= SK_FS; s_++) {
-                fpre[s_] = run;
-                const unsigned c_ = ld_u(&fc_in[s_]);
-                run += s_ < SK_FS && c_ > seg ? seg : c_;
-            }
-            fpre[SK_FS + 1] = run;
-        }
-        if (threadIdx.x < 3) ln[threadIdx.x] = 0;
-        __syncthreads();
-        const unsigned count = fpre[SK_FS + 1];
-        if (count == 0) {  // (the same for every workgroup: the counters were final at the barrier)
-            if (blockIdx.x == 0 && threadIdx.x == 0) st_u(&bar[2], (unsigned)r);  // rounds used (statistics)
+        if (!sk_sssp_one_round<true>(A, r, hops, glanes, lcap, blockDim.x)) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) st(&bar[2], (unsigned)r);  // rounds used (statistics)
             return;
         }
-        const unsigned* q = (r & 1) ? A.q1 : A.q0;
-        unsigned* qn = (r & 1) ? A.q0 : A.q1;
-        const unsigned round = (unsigned)r + 1u;
-#define SK_QPUSH(v_) st_u(&qn[sk_q_reserve_coop(qn, fc_out, seg, shard, 1u)], (v_))
-#define SK_RELAX_C(u, du, out, out_n)                                                                      \
-    {                                                                                                      \
-        const uint32_t s_ = A.row_off[u], e_ = A.row_off[(u) + 1];                                         \
-        for (uint32_t t = s_ + lane; t < e_; t += glanes) {                                                \
-            const unsigned v = A.col[t];                                                                   \
-            const unsigned o = st_f2ord((du) + A.wgt[t]);                                                  \
-            if (lookfirst && o >= ld_u(&A.dist_ord[v])) continue;                                          \
-            const unsigned old = atomicMin(&A.dist_ord[v], o);                                             \
-            if (o < old) {                                                                                 \
-                const unsigned slot = atomicAdd(out_n, 1u);                                                \
-                if (slot < SK_LQ) (out)[slot] = v;                                                         \
-                else if (atomicExch(&A.stamp[v], round) != round) SK_QPUSH(v);                             \
-            }                                                                                              \
-        }                                                                                                  \
-    }
-        for (unsigned f = gw; f < count; f += tw) {
-            int sh = 0;
-#pragma unroll
-            for (int s_ = 1; s_ <= SK_FS; s_++) sh = f >= fpre[s_] ? s_ : sh;
-            const unsigned u = ld_u(&q[(int64_t)sh * seg + (f - fpre[sh])]);
-            if (u == SK_Q_HOLE) continue;
-            const float du = st_ord2f(ld_u(&A.dist_ord[u]));
-            SK_RELAX_C(u, du, lq[0], &ln[0]);
-        }
-        int h = 1;
-        for (; h < hops; h++) {
-            __syncthreads();
-            const unsigned have = ln[(h - 1) % 3];
-            unsigned ncur = have < SK_LQ ? have : SK_LQ;
-            if (ncur == 0) break;
-            if (threadIdx.x == 0) ln[(h + 1) % 3] = 0;
-            const unsigned* in = lq[(h - 1) & 1];
-            unsigned* out = lq[h & 1];
-            if (ncur > (unsigned)lcap) {
-                for (unsigned i = lcap + threadIdx.x; i < ncur; i += blockDim.x) {
-                    const unsigned v = in[i];
-                    if (atomicExch(&A.stamp[v], round) != round) SK_QPUSH(v);
-                }
-                ncur = (unsigned)lcap;
-            }
-            for (unsigned i = wave; i < ncur; i += nwv) {
-                const unsigned u = in[i];
-                const float du = st_ord2f(ld_u(&A.dist_ord[u]));
-                SK_RELAX_C(u, du, out, &ln[h % 3]);
-            }
-        }
-#undef SK_RELAX_C
-        __syncthreads();
-        const unsigned have = ln[(h - 1) % 3];
-        const unsigned nrem = have < SK_LQ ? have : SK_LQ;
-        const unsigned* rem = lq[(h - 1) & 1];
-        unsigned* keep = lq[h & 1];
-        unsigned* keep_n = &ln[h % 3];
-        if (threadIdx.x == 0) *keep_n = 0;
-        __syncthreads();
-        for (unsigned i = threadIdx.x; i < nrem; i += blockDim.x) {
-            const unsigned v = rem[i];
-            if (atomicExch(&A.stamp[v], round) != round) keep[atomicAdd(keep_n, 1u)] = v;
-        }
-        __syncthreads();
-        const unsigned nloc = *keep_n;
-        if (threadIdx.x == 0 && nloc) lq_base = sk_q_reserve_coop(qn, fc_out, seg, shard, nloc);
-        __syncthreads();
-        for (unsigned i = threadIdx.x; i < nloc; i += blockDim.x) st_u(&qn[lq_base + i], keep[i]);
-#undef SK_QPUSH
         if (!sk_grid_barrier(bar, (unsigned)r)) return;
     }
 }
@@ -910,11 +827,6 @@ __device__ __forceinline__ void sk_chunk_boxes(const SkSelOne& O, float (*cb_lo)
     }
 }
 
-// agent-scope stores / loads of the job words (see SkJob)
-__device__ __forceinline__ void st_ai(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ld_ai(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ unsigned ld_au(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_au(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // Time-outs of the helper protocol (100 MHz wall clock; SkArgs.help_*; tuning codes 16-18 in microseconds).  They exist so that a
 // workgroup that never becomes resident cannot hang the GPU; none is an error: a helper whose life time ran out -- or whose component's
 // workgroup has not announced itself (`alive`) within `help_announce`: the chip is full of other work, the helper only takes a
@@ -975,11 +887,11 @@ __global__ void __launch_bounds__(1024) k_sk_select(SkArgs A) {
         const long long t_start = wall_clock64();
         for (;;) {
             if (tid == 0) {
-                h_seq = ld_au(&J->seq);
-                unsigned q_ = ld_au(&J->quit);
+                h_seq = ld(&J->seq);
+                unsigned q_ = ld(&J->quit);
                 if (!q_) {
                     const long long waited = wall_clock64() - t_start;
-                    if (waited > A.help_lifetime || (waited > A.help_announce && !ld_au(&J->alive))) { st_au(&J->gone, 1u); q_ = 1u; }
+                    if (waited > A.help_lifetime || (waited > A.help_announce && !ld(&J->alive))) { st(&J->gone, 1u); q_ = 1u; }
                 }
                 h_quit = q_;
             }
@@ -990,11 +902,11 @@ __global__ void __launch_bounds__(1024) k_sk_select(SkArgs A) {
             if (sq == seen) { __builtin_amdgcn_s_sleep(16); continue; }
             seen = sq;
             sk_acquire_agent();  // pairs with the release store of `seq`: the job words and the path are visible
-            const int len = ld_ai(&J->len), id = ld_ai(&J->id), csz = ld_ai(&J->csz), nrows = ld_ai(&J->nrows), ny = ld_ai(&J->ny);
-            const int x0 = ld_ai(&J->x0), y0 = ld_ai(&J->y0), z0 = ld_ai(&J->z0), z1 = ld_ai(&J->z1), poff = ld_ai(&J->path_off);
-            const float rp = __uint_as_float((unsigned)ld_ai((const int*)&J->rp));
+            const int len = ld(&J->len), id = ld(&J->id), csz = ld(&J->csz), nrows = ld(&J->nrows), ny = ld(&J->ny);
+            const int x0 = ld(&J->x0), y0 = ld(&J->y0), z0 = ld(&J->z0), z1 = ld(&J->z1), poff = ld(&J->path_off);
+            const float rp = __uint_as_float((unsigned)ld((const int*)&J->rp));
             for (int qi = tid; qi < len; qi += W) {  // the path (root side first) and its positions / radii
-                const int v = ld_ai(&A.path_verts[hbase + poff + qi]);
+                const int v = ld(&A.path_verts[hbase + poff + qi]);
                 const float4 q4 = A.pr[hbase + v];
                 L.one.lpx[qi] = q4.x; L.one.lpy[qi] = q4.y; L.one.lpz[qi] = q4.z; L.one.lpr[qi] = q4.w;
             }
@@ -1029,9 +941,9 @@ __global__ void __launch_bounds__(1024) k_sk_select(SkArgs A) {
     SkJob* J = &A.jobs[c];
     unsigned job_seq = 0u;
     if (B.in_lds) for (int i = tid; i < nwords; i += W) bm_words[i] = B.glb[i];
-    if (nhelp > 0 && tid == 0) st_au(&J->alive, 1u);  // (a helper that does not see this within `help_announce` gives up)
+    if (nhelp > 0 && tid == 0) st(&J->alive, 1u);  // (a helper that does not see this within `help_announce` gives up)
     __syncthreads();
-#define SK_QUIT_HELPERS() do { if (A.n_helpers > 0 && A.c_nhelp[c] > 0 && tid == 0) st_au(&J->quit, 1u); } while (0)  // (also when this workgroup does not use them: a component too large for the LDS bitmap)
+#define SK_QUIT_HELPERS() do { if (A.n_helpers > 0 && A.c_nhelp[c] > 0 && tid == 0) st(&J->quit, 1u); } while (0)  // (also when this workgroup does not use them: a component too large for the LDS bitmap)
 #define SK_FLUSH_BM()                                                             \
     do {                                                                          \
         __syncthreads();                                                          \
@@ -1470,7 +1382,7 @@ __global__ void __launch_bounds__(1024) k_sk_select(SkArgs A) {
         for (int qi = tid; qi < len; qi += blockDim.x) {
             const int w = len - 1 - qi;  // walk order -> root side first
             const int v = w < SK_LPATH ? L.one.lpath[w] : (int)ld_wg(&tmp[w]);
-            st_ai(&path_out[qi], v);  // (agent scope: the component's helper workgroups read the path)
+            st(&path_out[qi], v);  // (agent scope: the component's helper workgroups read the path)
             const float4 q4 = A.pr[base + v];
             const float r = q4.w;
             const unsigned long long k = (unsigned long long)st_f2ord(r) << 32;
@@ -1547,20 +1459,20 @@ __global__ void __launch_bounds__(1024) k_sk_select(SkArgs A) {
             bool help = nhelp > 0 && (nrows > 128 || len > 64);  // (a job costs ~5-10 us of hand-shake; such a claim > 50 us alone)
             int my_end = nrows;
             if (help) {
-                if (tid == 0) s_lost = ld_au(&J->gone);
+                if (tid == 0) s_lost = ld(&J->gone);
                 sk_release_agent();  // EVERY wavefront: its agent-scope stores of the path above have been performed ...
                 __syncthreads();     // ... before thread 0 publishes the job below
                 if (s_lost) {  // (uniform) a helper's life time ran out: alone from here on
-                    if (tid == 0) { st_au(&J->quit, 1u); st_au(&A.fcnt[0], 1u); }
+                    if (tid == 0) { st(&J->quit, 1u); st(&A.fcnt[0], 1u); }
                     help = false; nhelp = 0;
                 }
             }
             if (help) {
                 if (tid == 0) {
-                    st_ai(&J->len, len); st_ai(&J->id, id); st_ai(&J->csz, csz); st_ai(&J->nrows, nrows); st_ai(&J->ny, ny);
-                    st_ai(&J->x0, x0); st_ai(&J->y0, y0); st_ai(&J->z0, z0); st_ai(&J->z1, z1); st_ai(&J->path_off, cur_off);
-                    st_ai((int*)&J->rp, (int)__float_as_uint(rp));
-                    st_au(&J->done, 0u);
+                    st(&J->len, len); st(&J->id, id); st(&J->csz, csz); st(&J->nrows, nrows); st(&J->ny, ny);
+                    st(&J->x0, x0); st(&J->y0, y0); st(&J->z0, z0); st(&J->z1, z1); st(&J->path_off, cur_off);
+                    st((int*)&J->rp, (int)__float_as_uint(rp));
+                    st(&J->done, 0u);
                     // release: the job words (and, through the barrier above, the path) are performed before `seq` can be seen
                     __hip_atomic_store(&J->seq, ++job_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
                     if (A.ticks) A.ticks[14] += 1;
@@ -1575,12 +1487,12 @@ __global__ void __launch_bounds__(1024) k_sk_select(SkArgs A) {
                 if (tid == 0) {
                     const long long t0 = wall_clock64();
                     unsigned lost = 0u;
-                    while (ld_au(&J->done) < (unsigned)nhelp) {
+                    while (ld(&J->done) < (unsigned)nhelp) {
                         __builtin_amdgcn_s_sleep(12);  // (the helpers write to this line: do not hammer it)
-                        if (ld_au(&J->gone) != 0u || wall_clock64() - t0 > A.help_timeout) { lost = 1u; break; }
+                        if (ld(&J->gone) != 0u || wall_clock64() - t0 > A.help_timeout) { lost = 1u; break; }
                     }
                     s_lost = lost;
-                    if (lost) { st_au(&J->quit, 1u); st_au(&A.fcnt[0], 1u); }  // (fcnt[0]: a statistic -- helpers were lost in this call)
+                    if (lost) { st(&J->quit, 1u); st(&A.fcnt[0], 1u); }  // (fcnt[0]: a statistic -- helpers were lost in this call)
                 }
                 __syncthreads();
                 sk_acquire_agent();  // pairs with the helpers' release of `done`: their termination bits and branch ids are visible
@@ -1592,7 +1504,7 @@ __global__ void __launch_bounds__(1024) k_sk_select(SkArgs A) {
                 }
                 const unsigned* hw = A.help_bits + (base >> 5) + c;  // what the helpers terminated
                 for (int i = tid; i < nwords; i += W) {
-                    const unsigned w = ld_au(&hw[i]);
+                    const unsigned w = ld(&hw[i]);
                     if (B.in_lds) bm_words[i] |= w; else if (w) wg_or(&B.glb[i], w);
                 }
             }
@@ -1726,22 +1638,11 @@ __global__ void k_sk_helper_tables(SkArgs A, int* hl_comp, int* hl_rank, int* c_
 // ------------------------------------------------------------------------------- host side ---
 #define SK_GRID_CELLS (1ll << 24)
 
-struct SkLayout {
-    unsigned *dist_ord, *stamp, *q0, *q1, *touched, *cnt, *s_ntouched, *sort_keys, *order, *coop_bar;
-    float *s_rp, *order_init;
-    unsigned* term_bits;
-    float4* pr;
-    int *s_cursor, *s_wide;
-    char* sort_ws;
-    int64_t sort_bytes;
-    unsigned long long* best;
-    int *anc, *comp_of, *s_done, *s_len, *s_cur_id, *s_cur_off, *s_nb, *s_total, *blk_comp, *blk_first, *blk_count, *hl_comp, *hl_rank, *c_nhelp;
-    SkJob* jobs;
-    StGrid* g;
-    uint32_t* cell_start;
-    float4* recs;
-    char* gws;
-    int64_t gws_bytes;
+// the pieces of the workspace that only the host hands out (everything else goes to the kernels in SkArgs)
+struct SkHost {
+    unsigned *sort_keys, *coop_bar;
+    char *sort_ws, *gws;
+    int64_t sort_bytes, gws_bytes;
 };
 
 static inline int64_t sk_grid_cells(int nseg, int64_t m) {  // (st_grid_build uses at most 128 cells per point: size for that)
@@ -1754,46 +1655,48 @@ static inline int64_t sk_queue_words(int64_t m, int64_t C) { return SK_FS * sk_f
 // termination bits: component c owns the words from (comp_off[c] >> 5) + c, ceil(size / 32) of them
 static inline int64_t sk_term_words(int64_t m, int64_t C) { return m / 32 + C + 2; }
 
-static void sk_layout(StArena& a, int64_t m, int64_t C, SkLayout* s, int nseg = 1) {
-    s->dist_ord = a.take<unsigned>(m);
-    s->stamp = a.take<unsigned>(m);
-    s->q0 = a.take<unsigned>(sk_queue_words(m, C));  // SSSP frontier: SK_FS shard segments + the overflow area (sk_q_reserve)
-    s->q1 = a.take<unsigned>(sk_queue_words(m, C));
-    s->touched = a.take<unsigned>(m);
-    s->term_bits = a.take<unsigned>(2 * sk_term_words(m, C));  // the termination set, then the helpers' words
-    s->pr = a.take<float4>(m);
-    s->best = a.take<unsigned long long>(m);
-    s->anc = a.take<int>((int64_t)SK_ANC * m);
-    s->comp_of = a.take<int>(m);
-    s->cnt = a.take<unsigned>(8 + 3 * (SK_FS + 1));  // [8] counters, then the frontier counters of three generations
-    s->coop_bar = a.take<unsigned>(SK_COOP_STRIDE * (2 + SK_COOP_BLOCKS / SK_COOP_GROUP));  // grid barrier of the persistent SSSP
-    s->s_done = a.take<int>(C);
-    s->s_len = a.take<int>(C);
-    s->s_cur_id = a.take<int>(C);
-    s->s_cur_off = a.take<int>(C);
-    s->s_nb = a.take<int>(C);
-    s->s_total = a.take<int>(C);
-    s->s_rp = a.take<float>(C);
-    s->s_ntouched = a.take<unsigned>(C);
-    s->s_cursor = a.take<int>(C);
-    s->s_wide = a.take<int>(C);
-    s->sort_keys = a.take<unsigned>(m);
-    s->order = a.take<unsigned>(m);
-    s->order_init = a.take<float>(m);
-    s->sort_bytes = st_sort_ws_bytes(m);
-    s->sort_ws = a.take<char>(s->sort_bytes);
-    s->blk_first = a.take<int>(C);
-    s->blk_count = a.take<int>(C);
-    s->blk_comp = a.take<int>(C + st_div_up(m, 1024));
-    s->hl_comp = a.take<int>(SK_HELP_POOL);
-    s->hl_rank = a.take<int>(SK_HELP_POOL);
-    s->c_nhelp = a.take<int>(C);
-    s->jobs = a.take<SkJob>(C);
-    s->g = a.take<StGrid>(1);
-    s->cell_start = a.take<uint32_t>(sk_grid_cells(nseg, m) + 1);
-    s->recs = a.take<float4>(m);
-    s->gws_bytes = st_grid_ws_bytes(m, sk_grid_cells(nseg, m));
-    s->gws = a.take<char>(s->gws_bytes);
+// carves the workspace: the kernels' pointers straight into `A`, the host-only ones into `H`
+static void sk_layout(StArena& a, int64_t m, int64_t C, SkArgs* A, SkHost* H, int nseg = 1) {
+    A->dist_ord = a.take<unsigned>(m);
+    A->stamp = a.take<unsigned>(m);
+    A->q0 = a.take<unsigned>(sk_queue_words(m, C));  // SSSP frontier: SK_FS shard segments + the overflow area (sk_q_reserve)
+    A->q1 = a.take<unsigned>(sk_queue_words(m, C));
+    A->fseg = (unsigned)sk_fseg(m, C);
+    A->touched = a.take<unsigned>(m);
+    A->term_bits = a.take<unsigned>(2 * sk_term_words(m, C));  // the termination set, then the helpers' words
+    A->pr = a.take<float4>(m);
+    A->best = a.take<unsigned long long>(m);
+    A->anc = a.take<int>((int64_t)SK_ANC * m);
+    A->comp_of = a.take<int>(m);
+    A->cnt = a.take<unsigned>(8 + 3 * (SK_FS + 1));  // [8] counters, then the frontier counters of three generations
+    H->coop_bar = a.take<unsigned>(SK_COOP_STRIDE * (2 + SK_COOP_BLOCKS / SK_COOP_GROUP));  // grid barrier of the persistent SSSP
+    A->s_done = a.take<int>(C);
+    A->s_len = a.take<int>(C);
+    A->s_cur_id = a.take<int>(C);
+    A->s_cur_off = a.take<int>(C);
+    A->s_nb = a.take<int>(C);
+    A->s_total = a.take<int>(C);
+    A->s_rp = a.take<float>(C);
+    A->s_ntouched = a.take<unsigned>(C);
+    A->s_cursor = a.take<int>(C);
+    A->s_wide = a.take<int>(C);
+    H->sort_keys = a.take<unsigned>(m);
+    A->order = a.take<unsigned>(m);
+    A->order_init = a.take<float>(m);
+    H->sort_bytes = st_sort_ws_bytes(m);
+    H->sort_ws = a.take<char>(H->sort_bytes);
+    A->blk_first = a.take<int>(C);
+    A->blk_count = a.take<int>(C);
+    A->blk_comp = a.take<int>(C + st_div_up(m, 1024));
+    A->hl_comp = a.take<int>(SK_HELP_POOL);
+    A->hl_rank = a.take<int>(SK_HELP_POOL);
+    A->c_nhelp = a.take<int>(C);
+    A->jobs = a.take<SkJob>(C);
+    A->grid = a.take<StGrid>(1);
+    A->cell_start = a.take<uint32_t>(sk_grid_cells(nseg, m) + 1);
+    A->recs = a.take<float4>(m);
+    H->gws_bytes = st_grid_ws_bytes(m, sk_grid_cells(nseg, m));
+    H->gws = a.take<char>(H->gws_bytes);
 }
 
 // Tuning of one call (st_skeleton_components_seg's `tuning` argument: 16 x int64, entry = ST_TUNE_DEFAULT or NULL array =
@@ -1886,11 +1789,17 @@ extern "C" int st_abi_entries(int what) {
 
 extern "C" int64_t st_skeleton_workspace_bytes_seg(int64_t m, int64_t n_comp, int nseg) {
     StArena a(nullptr, 0);
-    SkLayout s;
-    sk_layout(a, m > 0 ? m : 1, n_comp > 0 ? n_comp : 1, &s, nseg);
+    SkArgs A;
+    SkHost H;
+    sk_layout(a, m > 0 ? m : 1, n_comp > 0 ? n_comp : 1, &A, &H, nseg);
     return a.used;
 }
 extern "C" int64_t st_skeleton_workspace_bytes(int64_t m, int64_t n_comp) { return st_skeleton_workspace_bytes_seg(m, n_comp, 1); }
+
+// SkArgs members that the kernels only read are const there; these pieces of the workspace are filled by the host's own
+// table-building launches (block and helper tables, claim grid, distance order), which get them writable through this
+template <class T>
+static inline T* sk_rw(const T* p) { return const_cast<T*>(p); }
 
 static inline unsigned sk_vgrid(int64_t m) {
     int64_t g = st_div_up(m > 0 ? m : 1, SK_WIDE_BLOCK);
@@ -1915,7 +1824,8 @@ static int sk_read(void* dst, const void* src, size_t bytes, hipStream_t stream)
 // [4] = their summed duration in ns, [5] = number of launches (profiling aid for bench.py's roofline block);
 // [6] = branches of the cloud | path vertices << 32 (sizes st_assemble_branches' outputs without a read-back of its own);
 // [8] = 1 if helper workgroups were lost in this call (time-outs: their component's workgroup did the work), [9] = helper workgroups launched,
-
+// [10] = the form of the SSSP that produced dist: 0 a launch per round, 1 the persistent launch completed, 2 the persistent
+// launch gave up at a barrier and the rounds were redone by launches (stage 1 only; tuning code 12).
 //
 // Batched form (st_skeleton_components_seg): the components of `nseg` independent clouds in one call.  comp_seg [C] = cloud
 // of each component, vert_seg_off [nseg + 1] = the clouds' ranges in the renumbered vertex space (both device arrays,
@@ -1941,27 +1851,19 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
     ST_REQUIRE(nseg == 1 || (comp_seg && vert_seg_off), "skeleton: a batch needs comp_seg and vert_seg_off");
     if (nseg == 1) { comp_seg = nullptr; vert_seg_off = nullptr; }
     StArena a(ws, ws_bytes);
-    SkLayout s;
-    sk_layout(a, m, n_comp, &s, nseg);
-    if (!a.ok() || !s.gws) {
+    SkArgs A;
+    SkHost H;
+    memset(&A, 0, sizeof(A));
+    sk_layout(a, m, n_comp, &A, &H, nseg);
+    if (!a.ok() || !H.gws) {
         st_set_error("skeleton: workspace too small (%lld < %lld)", (long long)ws_bytes, (long long)a.used);
         return ST_ERR_WORKSPACE;
     }
-    SkArgs A;
-    memset(&A, 0, sizeof(A));
-    A.C = n_comp; A.m = m; A.comp_off = comp_off; A.comp_seg = comp_seg; A.comp_of = s.comp_of; A.pts = pts; A.rad = rad; A.ysurf = ysurf;
-    A.row_off = row_off; A.col = col; A.wgt = wgt; A.grid = s.g; A.cell_start = s.cell_start; A.recs = s.recs;
+    A.C = n_comp; A.m = m; A.comp_off = comp_off; A.comp_seg = comp_seg; A.pts = pts; A.rad = rad; A.ysurf = ysurf;
+    A.row_off = row_off; A.col = col; A.wgt = wgt; A.help_bits = A.term_bits + sk_term_words(m, n_comp); A.fcnt = A.cnt + 8;
     A.dist = dist; A.pred = pred; A.root_local = root_local; A.tree_dist = tree_dist;
     A.branch_parent = branch_parent; A.branch_off = branch_off; A.branch_len = branch_len; A.n_branches = n_branches;
     A.path_verts = path_verts; A.branch_of = branch_of;
-    A.dist_ord = s.dist_ord; A.stamp = s.stamp; A.q0 = s.q0; A.q1 = s.q1; A.term_bits = s.term_bits; A.help_bits = s.term_bits + sk_term_words(m, n_comp); A.pr = s.pr;
-    A.best = s.best; A.touched = s.touched; A.anc = s.anc; A.cnt = s.cnt; A.fcnt = s.cnt + 8;
-    A.fseg = (unsigned)sk_fseg(m, n_comp);
-    A.s_done = s.s_done; A.s_len = s.s_len; A.s_cur_id = s.s_cur_id; A.s_cur_off = s.s_cur_off; A.s_nb = s.s_nb;
-    A.s_total = s.s_total; A.s_rp = s.s_rp; A.s_ntouched = s.s_ntouched;
-    A.blk_comp = s.blk_comp; A.blk_first = s.blk_first; A.blk_count = s.blk_count;
-    A.s_cursor = s.s_cursor; A.s_wide = s.s_wide; A.order = s.order; A.order_init = s.order_init;
-    A.hl_comp = s.hl_comp; A.hl_rank = s.hl_rank; A.c_nhelp = s.c_nhelp; A.jobs = s.jobs; A.n_helpers = 0;
     const SkTuning T(tuning);
     A.ticks = T.ticks;
     A.help_lifetime = T.help_lifetime_us * 100; A.help_timeout = T.help_timeout_us * 100; A.help_announce = T.help_announce_us * 100;
@@ -2006,9 +1908,9 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
     auto resolve_plateaus = [&](unsigned unresolved) -> int {
         unsigned round = 2;
         while (unresolved > 0) {
-            (void)hipMemsetAsync(&s.cnt[4], 0, sizeof(unsigned), stream);
+            (void)hipMemsetAsync(&A.cnt[4], 0, sizeof(unsigned), stream);
             hipLaunchKernelGGL(k_sk_preds_plateau, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, round);
-            ST_TRY(sk_read(h, s.cnt, sizeof(unsigned) * 8, stream));
+            ST_TRY(sk_read(h, A.cnt, sizeof(unsigned) * 8, stream));
             if (h[4] == 0) break;  // unreachable leftovers (cannot happen inside a component)
             unresolved -= h[4];
             round++;
@@ -2018,10 +1920,12 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
     };
     // Roots, SSSP, canonical predecessors (not the plateau rounds).
     auto run_sssp = [&]() -> int {
-        hipLaunchKernelGGL(k_sk_init, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A);
-        hipLaunchKernelGGL(k_sk_roots, dim3((unsigned)n_comp), dim3((unsigned)block_threads), 0, stream, A);
-        bool coop_done = false;
-
+        auto start = [&]() {  // distances, stamps and counters reset; round 0's frontier = every component's root
+            hipLaunchKernelGGL(k_sk_init, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A);
+            hipLaunchKernelGGL(k_sk_roots, dim3((unsigned)n_comp), dim3((unsigned)block_threads), 0, stream, A);
+        };
+        start();
+        int form = 0;  // stats_host[10]: 0 a launch per round, 1 the persistent launch completed, 2 it gave up and the rounds were redone by launches
         if (T.sssp_coop) {
             // every round in ONE launch (k_sk_sssp_coop); one read-back tells whether a workgroup gave up at a barrier
             // the grid must be resident as a whole: at most four workgroups of 256 lanes per compute unit (1024 on an MI355X; a device
@@ -2029,22 +1933,19 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
             const int cus = sk_cu_count();
             const unsigned resident = cus > 1 ? (unsigned)st_min64(4ll * cus, SK_COOP_BLOCKS) : 1u;
             const unsigned cg = fg < resident ? fg : resident;
-            (void)hipMemsetAsync(s.coop_bar, 0, SK_COOP_STRIDE * (2 + SK_COOP_BLOCKS / SK_COOP_GROUP) * sizeof(unsigned), stream);
-            hipLaunchKernelGGL(k_sk_sssp_coop, dim3(cg), dim3(SK_WIDE_BLOCK), 0, stream, A, T.sssp_hops, T.sssp_lanes, T.sssp_lcap, s.coop_bar, 1 << 24);
+            (void)hipMemsetAsync(H.coop_bar, 0, SK_COOP_STRIDE * (2 + SK_COOP_BLOCKS / SK_COOP_GROUP) * sizeof(unsigned), stream);
+            hipLaunchKernelGGL(k_sk_sssp_coop, dim3(cg), dim3(SK_WIDE_BLOCK), 0, stream, A, T.sssp_hops, T.sssp_lanes, T.sssp_lcap, H.coop_bar, 1 << 24);
             unsigned hb[4];
-            ST_TRY(sk_read(hb, s.coop_bar, sizeof(hb), stream));
-            if (hb[1] == 0u) { coop_done = true; sssp_rounds = hb[2]; }
-            else {  // start over, one launch per round
-                hipLaunchKernelGGL(k_sk_init, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A);
-                hipLaunchKernelGGL(k_sk_roots, dim3((unsigned)n_comp), dim3((unsigned)block_threads), 0, stream, A);
-            }
+            ST_TRY(sk_read(hb, H.coop_bar, sizeof(hb), stream));
+            if (hb[1] == 0u) { form = 1; sssp_rounds = hb[2]; }
+            else { form = 2; start(); }  // start over, one launch per round
         }
-        for (int r = 0; !coop_done;) {  // frontier rounds in batches, one counter read-back per batch.  The first batch is twice as long:
+        for (int r = 0; form != 1;) {  // frontier rounds in batches, one counter read-back per batch.  The first batch is twice as long:
             // a tree of a million points needs 65-96 launches, an empty round costs ~4 us, a read-back beside other clouds ~1 ms
             const int batch = r == 0 ? T.sssp_first * T.sssp_batch : T.sssp_batch;
             for (int b = 0; b < batch; b++, r++)
                 hipLaunchKernelGGL(k_sk_sssp_round, dim3(fg), dim3(SK_WIDE_BLOCK), 0, stream, A, r, T.sssp_hops, T.sssp_lanes, T.sssp_lcap);
-            ST_TRY(sk_read(h, s.cnt, sizeof(h), stream));
+            ST_TRY(sk_read(h, A.cnt, sizeof(h), stream));
             sssp_rounds = r;
             unsigned left = 0;  // entries of the frontier the next launch would read
             for (int i = 0; i <= SK_FS; i++) left |= h[8 + (r % 3) * (SK_FS + 1) + i];
@@ -2053,7 +1954,7 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
         }
         hipLaunchKernelGGL(k_sk_dist_out, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A);
         hipLaunchKernelGGL(k_sk_preds, dim3((unsigned)st_min64(st_div_up(m * SK_PRED_LANES, SK_WIDE_BLOCK), 8192)), dim3(SK_WIDE_BLOCK), 0, stream, A);
-        if (stats_host) stats_host[0] = sssp_rounds;
+        if (stats_host) { stats_host[0] = sssp_rounds; stats_host[10] = form; }
         return ST_OK;
     };
     if (stages & 1) {
@@ -2062,7 +1963,7 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
         // next, their count is not read back here (a blocking round trip costs ~1 ms beside other clouds' kernels,
         // DESIGN.md section 5) but arrives with the first progress read-back of the select loop, which is then redone.
         if (!defer_plateaus) {
-            ST_TRY(sk_read(h, s.cnt, sizeof(unsigned) * 8, stream));
+            ST_TRY(sk_read(h, A.cnt, sizeof(unsigned) * 8, stream));
             ST_TRY(resolve_plateaus(h[3]));
         }
     }
@@ -2073,7 +1974,7 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
         for (int r = 0;;) {
             for (int b = 0; b < 32; b++, r++)
                 hipLaunchKernelGGL(k_sk_td_round, dim3(fg), dim3(SK_WIDE_BLOCK), 0, stream, A, r);
-            ST_TRY(sk_read(h, s.cnt, sizeof(unsigned) * 8, stream));
+            ST_TRY(sk_read(h, A.cnt, sizeof(unsigned) * 8, stream));
             if (h[r % 3] == 0) break;
             ST_REQUIRE(r < (1 << 24), "skeleton: tree distance did not converge");
         }
@@ -2081,13 +1982,13 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
     if (stages & 4) {
         // claim / finalize grid: workgroups per component proportional to its size, laid out by k_sk_blk_tables
         const int nblk = (int)st_min64((int64_t)n_comp + st_div_up(m, 1024), (int64_t)n_comp * SK_MAX_CLAIM_BLOCKS);
-        hipLaunchKernelGGL(k_sk_blk_tables, dim3(1), dim3(1024), 0, stream, A, s.blk_comp, s.blk_first, s.blk_count, nblk);
+        hipLaunchKernelGGL(k_sk_blk_tables, dim3(1), dim3(1024), 0, stream, A, sk_rw(A.blk_comp), sk_rw(A.blk_first), sk_rw(A.blk_count), nblk);
         // helper workgroups of the long-path claims (they sit in front of the components' workgroups in the grid, so they are
         // normally resident before any component can wait for them; if not, the time-outs above apply)
         A.n_helpers = lease.n;
-        hipLaunchKernelGGL(k_sk_helper_tables, dim3(1), dim3(64), 0, stream, A, s.hl_comp, s.hl_rank, s.c_nhelp);
+        hipLaunchKernelGGL(k_sk_helper_tables, dim3(1), dim3(64), 0, stream, A, sk_rw(A.hl_comp), sk_rw(A.hl_rank), sk_rw(A.c_nhelp));
         // grid_cell < 0: cell = max(rad) / -grid_cell with the maximum reduced on the device (no host round trip)
-        ST_TRY(st_grid_build(pts, m, grid_cell, sk_grid_cells(nseg, m), s.g, s.cell_start, s.recs, s.gws, s.gws_bytes, stream,
+        ST_TRY(st_grid_build(pts, m, grid_cell, sk_grid_cells(nseg, m), sk_rw(A.grid), sk_rw(A.cell_start), sk_rw(A.recs), H.gws, H.gws_bytes, stream,
                              grid_cell < 0.0f ? -1.0f : 0.0f, grid_cell < 0.0f ? rad : nullptr, grid_cell < 0.0f ? m : 0,
                              vert_seg_off, nseg, vert_seg_off, T.grid_mean_mult));
         int64_t iters = 0;
@@ -2104,22 +2005,22 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
         double select_ms = 0.0;
         bool plateaus_pending = defer_plateaus;
         for (;;) {  // second pass only if the deferred check found plateau vertices: predecessors completed, selection redone
-            (void)hipMemsetAsync(&s.cnt[5], 0, 4 * sizeof(unsigned), stream);  // finished components, branches, path vertices; fcnt[0] = helper time-out flag
+            (void)hipMemsetAsync(&A.cnt[5], 0, 4 * sizeof(unsigned), stream);  // finished components, branches, path vertices; fcnt[0] = helper time-out flag
             const float* distances = (stages & 2) ? tree_dist : dist;
-            (void)hipMemsetAsync(s.term_bits, 0, 2 * sk_term_words(m, n_comp) * sizeof(unsigned), stream);
+            (void)hipMemsetAsync(A.term_bits, 0, 2 * sk_term_words(m, n_comp) * sizeof(unsigned), stream);
             hipLaunchKernelGGL(k_sk_lift_init, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A);
             for (int span = 1; span < SK_ANC; span *= 2)  // direct ancestor table by doubling
                 hipLaunchKernelGGL(k_sk_anc_pass, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, span);
             // order the vertices of every component by distance, once: the per-branch argmax becomes a cursor
-            hipLaunchKernelGGL(k_sk_sort_keys, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, distances, s.sort_keys, s.order, 0);
-            ST_TRY(st_radix_sort_pairs_u32(s.sort_keys, s.order, m, 32, s.sort_ws, s.sort_bytes, stream));
+            hipLaunchKernelGGL(k_sk_sort_keys, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, distances, H.sort_keys, sk_rw(A.order), 0);
+            ST_TRY(st_radix_sort_pairs_u32(H.sort_keys, sk_rw(A.order), m, 32, H.sort_ws, H.sort_bytes, stream));
             if (n_comp > 1) {
                 int bits = 1;
                 while ((1ll << bits) < n_comp) bits++;
-                hipLaunchKernelGGL(k_sk_sort_keys, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, distances, s.sort_keys, s.order, 1);
-                ST_TRY(st_radix_sort_pairs_u32(s.sort_keys, s.order, m, bits, s.sort_ws, s.sort_bytes, stream));
+                hipLaunchKernelGGL(k_sk_sort_keys, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, distances, H.sort_keys, sk_rw(A.order), 1);
+                ST_TRY(st_radix_sort_pairs_u32(H.sort_keys, sk_rw(A.order), m, bits, H.sort_ws, H.sort_bytes, stream));
             }
-            hipLaunchKernelGGL(k_sk_order_init, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, distances, s.order_init);
+            hipLaunchKernelGGL(k_sk_order_init, dim3(vg), dim3(SK_WIDE_BLOCK), 0, stream, A, distances, sk_rw(A.order_init));
             iters = 0;
             select_ms = 0.0;
             bool redo = false;
@@ -2128,13 +2029,13 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
             for (int batch = first_launches;; batch = batch > 4 ? 4 : batch) {  // launch pairs per counter read-back: a long first
                 // batch, short ones for the stragglers (a finished launch pair still costs its ~10 us of launch latency)
                 for (int b = 0; b < batch; b++, iters++) {
-                    if (A.n_helpers > 0) (void)hipMemsetAsync(s.jobs, 0, (size_t)n_comp * sizeof(SkJob), stream);
+                    if (A.n_helpers > 0) (void)hipMemsetAsync(A.jobs, 0, (size_t)n_comp * sizeof(SkJob), stream);
                     if (time_sel) (void)hipEventRecord(ev[2 * b], stream);
                     hipLaunchKernelGGL(k_sk_select, dim3((unsigned)(A.n_helpers + n_comp)), dim3((unsigned)block_threads), 0, stream, A);
                     if (time_sel) (void)hipEventRecord(ev[2 * b + 1], stream);
                     hipLaunchKernelGGL(k_sk_claim, dim3((unsigned)nblk), dim3(SK_WIDE_BLOCK), 0, stream, A);
                 }
-                ST_TRY(sk_read(h, s.cnt, sizeof(unsigned) * 9, stream));  // (h[8] = fcnt[0]: helper workgroups were lost -- their
+                ST_TRY(sk_read(h, A.cnt, sizeof(unsigned) * 9, stream));  // (h[8] = fcnt[0]: helper workgroups were lost -- their
                 // component's workgroup did the work itself: slower, not wrong)
                 if (time_sel)
                     for (int b = 0; b < batch; b++) {
@@ -2151,9 +2052,9 @@ extern "C" int st_skeleton_components_seg(int n_comp, const int32_t* comp_off, c
             }
             if (!redo) break;
             // plateau vertices left unresolved: redo the predecessor pass with its resolved / unresolved marks, then the plateaus
-            (void)hipMemsetAsync(&s.cnt[3], 0, sizeof(unsigned), stream);
+            (void)hipMemsetAsync(&A.cnt[3], 0, sizeof(unsigned), stream);
             hipLaunchKernelGGL(k_sk_preds, dim3((unsigned)st_min64(st_div_up(m * SK_PRED_LANES, SK_WIDE_BLOCK), 8192)), dim3(SK_WIDE_BLOCK), 0, stream, A);
-            ST_TRY(sk_read(h, s.cnt, sizeof(unsigned) * 8, stream));
+            ST_TRY(sk_read(h, A.cnt, sizeof(unsigned) * 8, stream));
             ST_TRY(resolve_plateaus(h[3]));
         }
         if (time_select) {  // [5] = 0 tells the caller that no (trustworthy) timing was taken

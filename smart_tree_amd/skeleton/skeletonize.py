@@ -111,7 +111,7 @@ def run_components(comps: ComponentSet, medial_pts: torch.Tensor, radius: torch.
             _lib.ptr(res.path_verts), _lib.ptr(res.branch_of), stats, _lib.ptr(ws), ws.numel(), _lib.stream(dev),
             tuning.skeleton_array()))
     res.stats = {"sssp_rounds": stats[0], "plateau_rounds": stats[1], "select_launches": stats[2], "lift_levels": stats[3],
-                 "helpers_lost": int(stats[8]), "helpers": int(stats[9])}
+                 "helpers_lost": int(stats[8]), "helpers": int(stats[9]), "sssp_form": int(stats[10])}
     _note_helpers(res.stats)
     if stages & STAGE_SAMPLE:  # cloud totals from the select loop's last progress read-back
         res.stats["branches"], res.stats["path_vertices"] = int(stats[6] & 0xFFFFFFFF), int(stats[6] >> 32)

@@ -117,7 +117,8 @@ def _prepare_components(backend, pts, mv, cache_key=None):
     return out
 
 
-def _compare_components(backend, pts, mv, block_threads, cache_key=None):
+def _compare_components(backend, pts, mv, block_threads, cache_key=None, stats_out=None):
+    """Returns the number of branches; `stats_out` (a dict) receives the run's `res.stats`."""
     ref, comps, medial, radius, ys = _prepare_components(backend, pts, mv, cache_key)
     res = run_components(comps, medial, radius, ys,
                          stages=STAGE_SSSP | STAGE_TREE_DISTANCE | STAGE_SAMPLE, block_threads=block_threads)
@@ -143,6 +144,8 @@ def _compare_components(backend, pts, mv, block_threads, cache_key=None):
     assert res.stats["branches"] == n_branches
     assert res.stats["path_vertices"] == sum(len(br.verts) for rc in ref.components for br in rc.branches)
     DeviceSkeleton.from_components(comps, res, medial, radius, verify_counts=True)  # asserts equality with its own counts
+    if stats_out is not None:
+        stats_out.update(res.stats)
     return n_branches
 
 
@@ -166,14 +169,49 @@ def test_components_match_oracle(backend):
     {6: 6, 13: 2, 10: 3},        # ... three workgroups, at most two vertices per workgroup and local level (the rest goes back)
     {12: 1},                     # SSSP: every round in ONE persistent launch with grid barriers
     {12: 1, 6: 7, 10: 3},        # ... seven levels per round, three workgroups
+    {13: 0},                     # SSSP: no look before the atomic
+    {12: 1, 13: 0},              # ... in the persistent launch
+    {12: 1, 6: 6, 13: 2, 10: 3},  # ... the per-level cap and the overflow push (sssp-cap) in the persistent launch
 ], ids=["noprune", "prune4", "relaunch", "one", "long", "local", "wide", "mixed", "mixed-wide", "sssp-rows",
-        "sssp-hops", "sssp-cap", "sssp-coop", "sssp-coop-hops"])
+        "sssp-hops", "sssp-cap", "sssp-coop", "sssp-coop-hops", "sssp-nolook", "sssp-coop-nolook", "sssp-coop-cap"])
 def test_sample_tree_strategies_agree(backend, params):
-    """Branch selection has four claim strategies picked by size; each one alone must reproduce the oracle."""
+    """Branch selection has four claim strategies picked by size; each one alone must reproduce the oracle.  So must either
+    form of the SSSP, and the result must come from the form that was asked for: the host redoes a persistent launch that
+    gave up at a barrier with a launch per round, which is just as correct -- stats["sssp_form"] tells the two apart."""
     from smart_tree_amd.skeleton import tuning
     pts, mv = _tree()
+    stats = {}
     with tuning.override(params):  # per call: the library has no process-global knobs
-        assert _compare_components(backend, pts, mv, block_threads=256, cache_key="strategies") >= 2
+        assert _compare_components(backend, pts, mv, block_threads=256, cache_key="strategies", stats_out=stats) >= 2
+    assert stats["sssp_form"] == (1 if params.get(12, 0) & 1 else 0)
+
+
+def test_persistent_sssp_across_barrier_groups(backend):
+    """More than 32 * 256 graph vertices: the persistent launch has more workgroups than one group of its two-level grid
+    barrier holds (SK_COOP_GROUP = 32 workgroups of 256 lanes), so a round ends only when several groups have arrived.
+    Roots, distances and predecessors are the oracle's, bit for bit, and they come from the persistent launch itself."""
+    from smart_tree_amd.skeleton import tuning
+    pts, mv = _tree(n=40000, voxel=0.02)  # ~10k graph vertices: 40 workgroups, two barrier groups
+    ref = so.skeletonize(pts, mv, K=16, min_connection_length=0.02, minimum_graph_vertices=32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(backend)
+    keep = ref.keep_mask.astype(bool)
+    # (the oracle's own edge list: the searches that build it are test_outlier_and_graph_match_oracle's business, and slow emulated)
+    medial, radius = G.medial_points(t(pts[keep]), t(mv[keep]))
+    comps = Graph(medial, t(ref.edges), t(ref.weights)).connected_cugraph_components(minimum_vertices=32)
+    assert comps.n_components == len(ref.components)
+    ys = t(pts[keep][:, 1])
+    m = int(comps.comp_off[-1])
+    assert m > 32 * 256, m
+    with tuning.override({12: 1}):
+        res = run_components(comps, medial, radius, ys, stages=STAGE_SSSP)
+    off = comps.comp_off.cpu().numpy()
+    for c, rc in enumerate(ref.components):
+        a, b = off[c], off[c + 1]
+        np.testing.assert_array_equal(comps.vert_order[a:b].cpu().numpy(), rc.vertex_ids)
+        assert int(res.root_local[c]) == rc.root
+        np.testing.assert_array_equal(res.dist[a:b].cpu().numpy(), rc.dist)
+        np.testing.assert_array_equal(res.pred[a:b].cpu().numpy(), rc.preds)
+    assert res.stats["sssp_form"] == 1
 
 
 @pytest.mark.parametrize("mults", [(0, 0), (100, 45), (25, 15)], ids=["max-only", "default", "fine"])

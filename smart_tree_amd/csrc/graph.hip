@@ -540,6 +540,7 @@ extern "C" int st_component_layout_seg(const int32_t* labels, int64_t n, int min
     ST_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_fill_i32, dim3(g), dim3(GR_BLOCK), 0, stream, new_id, n, -1);
     if (C == 0) {
+        (void)hipMemsetAsync(comp_off, 0, sizeof(int32_t), stream);  // comp_off [C + 1]: the one entry an empty layout has
         if (nseg > 1) { (void)hipMemsetAsync(comp_seg_off, 0, (nseg + 1) * sizeof(int32_t), stream); (void)hipMemsetAsync(vert_seg_off, 0, (nseg + 1) * sizeof(int32_t), stream); }
         ST_CHECK_LAUNCH();
         return ST_OK;

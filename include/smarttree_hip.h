@@ -32,7 +32,8 @@ extern "C" {
  * st_component_csr_knn_workspace_bytes asks for one more int32 per table entry.
  * 107: st_synth_points_seg and st_synth_philox added (no existing signature changed).
  * 108: st_prediction_metrics and its three size queries added (no existing signature changed).
- * 109: the st_render_* calls added (no existing signature changed). */
+ * 109: the st_render_* calls added (no existing signature changed).
+ * 110: st_bridge_components_seg and its size query added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -519,6 +520,26 @@ int st_render_segments(const float* a, const float* b, const float* r1, const fl
                        const float* cams, int V, int H, int W, float near, void* ws, int64_t ws_bytes, void* stream);
 int st_render_resolve(const StRenderItem* items_host, int n_items, int V, int H, int W, float edl_strength, int edl_px,
                       uint8_t* rgb, float* depth, int32_t* ids, void* ws, int64_t ws_bytes, void* stream);
+
+/* ---- skeleton stage: bridging components across gaps (csrc/bridge.hip) -------------------------------------
+ * The reference stops short of this (skeleton/connection.py is a stub, data_types/tree.py:connect only draws a line): a branch
+ * whose medial points are cut by occlusion comes back as separate trees.  The bridges are edges to ADD TO THE GRAPH before the
+ * shortest-path stage.
+ *
+ * Input: the layout of st_component_layout_seg -- vert_order [m] (original ids of the kept vertices, components contiguous),
+ * new_id [n], comp_off [n_comp + 1], and for a batch vert_seg_off [nseg + 1], the clouds' ranges in the renumbered vertex space
+ * (NULL / nseg = 1: one cloud) -- and the vertex positions pts [n,3].  Only kept vertices take part.
+ * Candidates: vertex pairs in different components of one cloud with d2 <= max_gap * max_gap (float32 product, formed once),
+ * d2 = (dx*dx + dy*dy) + dz*dz in float32 without contraction.  Strict total order (bits of d2, lo id, hi id).  The bridges are
+ * the minimum spanning forest of the component graph under that order: edges [B,2] int64 (original ids, lo < hi), weights [B] =
+ * sqrtf(d2), in the order of the components they hook; B <= n_comp - 1 <= cap is written to *n_bridges_host.
+ * stats_host (optional, 4 x int64, zeroed and written): Boruvka rounds, boundary vertices of round 1, bridges, 0.
+ * m = 0, n_comp <= 1 or max_gap <= 0 (or NaN): zero bridges, nothing launched.  Waits for the stream once per round. */
+int64_t st_bridge_components_workspace_bytes(int64_t m, int64_t n_comp, int nseg);
+int st_bridge_components_seg(const float* pts, int64_t n, const int32_t* vert_order, int64_t m, const int32_t* new_id,
+                             const int32_t* comp_off, int64_t n_comp, const int32_t* vert_seg_off, int nseg, float max_gap,
+                             int64_t* edges, float* weights, int64_t cap, int64_t* n_bridges_host, int64_t* stats_host, void* ws,
+                             int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,36 @@ def connected_components(graph: Graph, minimum_vertices: int = 0) -> ComponentSe
                         nseg, comp_seg[:C] if comp_seg is not None else None, comp_seg_off, vert_seg_off)
 
 
+last_bridge_stats: dict = {}  # of the most recent bridge_components call of this process (diagnostics: tools/bench_bridge.py)
+
+
+def bridge_components(comps: ComponentSet, points: torch.Tensor, max_gap: float):
+    """Edges that join the kept components of `comps` across gaps of at most `max_gap` (csrc/bridge.hip; the reference's
+    skeleton/connection.py never got this far).  Candidates are the vertex pairs of different components of one cloud with
+    d2 = (dx*dx + dy*dy) + dz*dz <= max_gap^2 in float32; the bridges are the minimum spanning forest of the component graph
+    under the strict order (d2 bits, lo, hi).  Returns (edges [B,2] int64 in original vertex ids with lo < hi, weights [B]
+    float32 = sqrt(d2)): edges to add to the graph the components came from.  Vertices of dropped components take no part."""
+    global last_bridge_stats
+    L = _lib.lib()
+    dev = points.device
+    C, m, n = comps.n_components, int(comps.vert_order.shape[0]), int(points.shape[0])
+    max_gap = float(max_gap)
+    pts = points.contiguous().float()
+    cap = max(C - 1, 1)
+    edges = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+    weights = torch.empty((cap,), dtype=torch.float32, device=dev)
+    nb, stats = ctypes.c_int64(0), (ctypes.c_int64 * 4)()
+    if C > 1 and m > 0 and max_gap > 0.0:  # (otherwise the library would launch nothing either)
+        nseg = comps.n_seg
+        ws = _lib.workspace(L.st_bridge_components_workspace_bytes(m, C, nseg), dev)
+        _lib.check(L.st_bridge_components_seg(
+            _lib.ptr(pts), n, _lib.ptr(comps.vert_order.contiguous()), m, _lib.ptr(comps.new_id.contiguous()),
+            _lib.ptr(comps.comp_off.contiguous()), C, _lib.ptr(comps.vert_seg_off) if nseg > 1 else None, nseg, max_gap,
+            _lib.ptr(edges), _lib.ptr(weights), cap, ctypes.byref(nb), stats, _lib.ptr(ws), ws.numel(), _lib.stream(dev)))
+    last_bridge_stats = {"rounds": int(stats[0]), "boundary": int(stats[1]), "bridges": int(nb.value)}
+    return edges[: nb.value], weights[: nb.value]
+
+
 def remap_edges(edges: torch.Tensor) -> torch.Tensor:
     """graph.py:94-104: renumber vertex ids by rank (kept for API parity; the kernels use ComponentSet.new_id)."""
     _, inverse = torch.unique(edges, return_inverse=True)

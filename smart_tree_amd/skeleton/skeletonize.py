@@ -21,7 +21,8 @@ from ..data_types.cloud import Cloud
 from ..data_types.tree import DisjointTreeSkeleton, TreeSkeleton
 from .filter import outlier_removal
 from . import tuning
-from .graph import ComponentSet, medial_points, nn_graph
+from ..data_types.graph import Graph
+from .graph import ComponentSet, bridge_components, connected_components, medial_points, nn_graph
 
 STAGE_SSSP, STAGE_TREE_DISTANCE, STAGE_SAMPLE = 1, 2, 4
 
@@ -129,7 +130,15 @@ def run_components(comps: ComponentSet, medial_pts: torch.Tensor, radius: torch.
 
 class Skeletonizer:
     def __init__(self, K: int, min_connection_length: float, minimum_graph_vertices: int,
-                 device: torch.device = torch.device("cuda:0")):
+                 device: torch.device = torch.device("cuda:0"), connect_components: bool = False, max_gap: float = 0.0):
+        """connect_components / max_gap (additive; the reference's skeleton/connection.py is an unfinished stub): components of
+        the neighbourhood graph whose medial points come within `max_gap` metres of each other are joined by the shortest such
+        edges (skeleton.graph.bridge_components) before the shortest-path stage, so a branch cut by occlusion hangs on its
+        parent instead of coming back as a tree of its own.  Trees farther apart than max_gap stay separate."""
+        if connect_components and not float(max_gap) > 0.0:
+            raise ValueError(f"Skeletonizer: connect_components needs max_gap > 0 (got {max_gap})")
+        self.connect_components = bool(connect_components)
+        self.max_gap = float(max_gap)
         self.K = K
         self.min_connection_length = min_connection_length
         self.minimum_graph_vertices = minimum_graph_vertices
@@ -161,6 +170,15 @@ class Skeletonizer:
             graph = nn_graph(medial, radius.clamp(min=self.min_connection_length), K=self.K, seg_off=cloud.seg_off)
         with profiling.stage("components"):
             comps = graph.connected_cugraph_components(minimum_vertices=self.minimum_graph_vertices)
+        if self.connect_components:
+            with profiling.stage("bridge_components"):
+                bridges, bridge_w = bridge_components(comps, medial, self.max_gap)
+                if bridges.shape[0] > 0:
+                    # the graph plus the bridges through the edge-list path: labels, layout and adjacency as for any Graph.
+                    # (No bridge: the ComponentSet above is used as it is -- the feature then changes nothing at all.)
+                    joined = Graph(medial, torch.cat((graph.edges, bridges)), torch.cat((graph.edge_weights, bridge_w)))
+                    joined.seg_off = cloud.seg_off
+                    comps = connected_components(joined, self.minimum_graph_vertices)
         if self.on_wide_phase_done is not None:
             self.on_wide_phase_done()
         with profiling.stage("sssp_sample_tree"):

@@ -24,6 +24,7 @@
 //     (rounds 1-2: one blocking read-back per strided level).  Tables are laid out with a row stride = the level's capacity.
 #include "st_common.h"
 #include "st_grid.h"  // ST_MAX_SEG
+#include "st_rule.h"
 
 #define BK_BLOCK 256
 #define BK_MAX_DEPTH 6
@@ -48,7 +49,7 @@ struct BkLevel {
 };
 
 struct BkState {
-    int ext[ST_MAX_SEG][3];  // level-0 extent (largest z, y, x) of every cloud; level l clips at ext >> l
+    int ext[ST_MAX_SEG][3];  // level-0 extent (largest z, y, x) of every cloud; level l clips at st_rule_omax(ext, l)
     unsigned fail;           // bit 0: a capacity was exceeded, bit 1: a coordinate outside the declared bound
 };
 
@@ -98,8 +99,7 @@ static inline unsigned bk_grid(int64_t n) {
 __global__ void __launch_bounds__(BK_BLOCK) k_bk_mark0(const int32_t* coords, int64_t n, BkLevel L, BkState* st, const int32_t* blk_seg,
                                                        int nseg, int nblk) {
     __shared__ int m[ST_MAX_SEG * 3];
-    for (int i = threadIdx.x; i < nseg * 3; i += blockDim.x) m[i] = 0;
-    __syncthreads();
+    st_ext_clear(m, nseg);
     const int lim = 8 << L.mb;
     BK_LOOP(i, n) {
         const int4 c = reinterpret_cast<const int4*>(coords)[i];  // (b, z, y, x)
@@ -108,13 +108,9 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_mark0(const int32_t* coords, in
             continue;
         }
         L.p[bk_tab(L, c.x, c.y, c.z, c.w)] = 1u;
-        const int s = blk_seg ? blk_seg[c.x] : 0;
-        if (c.y > m[3 * s]) atomicMax(&m[3 * s], c.y);
-        if (c.z > m[3 * s + 1]) atomicMax(&m[3 * s + 1], c.z);
-        if (c.w > m[3 * s + 2]) atomicMax(&m[3 * s + 2], c.w);
+        st_ext_offer(m, blk_seg ? blk_seg[c.x] : 0, c.y, c.z, c.w);
     }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nseg * 3; i += blockDim.x) if (m[i]) atomicMax(&(&st->ext[0][0])[i], m[i]);
+    st_ext_flush(m, nseg, &st->ext[0][0]);
 }
 
 // occupied bricks get an empty record that remembers its table index (after the scan of the flags)
@@ -237,9 +233,8 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_subm(const int32_t* coords, con
     }
 }
 
-// ---- coarse active set of the strided convolution (k3 s2 p1): coarse o is active iff a fine voxel sits at 2o - 1 + k, k in 0..2 per
-// axis, and 0 <= o <= ext / 2.  Computed brick by brick on the MASKS (a stencil on bit planes), not voxel by voxel: a fine
-// voxel offers itself to up to 8 outputs and ~6 fine voxels share an output -- per voxel that was 3.4 look-ups + bit-sets each
+// ---- coarse active set of the strided convolution (the rule of st_rule.h).  Computed brick by brick on the MASKS (a stencil on
+// bit planes), not voxel by voxel: a fine voxel offers itself to up to 8 outputs and ~6 fine voxels share an output -- per voxel that was 3.4 look-ups + bit-sets each
 // (27 us per cloud at 24 clouds per launch set); per coarse brick it is 27 fine-brick look-ups for 512 outputs.
 // PASS A: every occupied fine brick fb flags the coarse bricks it can reach: fb >> 1 per axis, and (fb >> 1) + 1 when fb is odd
 // and the brick has a voxel on its last layer of that axis (fine c = 8 fb + 7 -> o = 4 fb + 4).
@@ -266,7 +261,7 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_coarse_mark(BkLevel Lf, BkLevel
 #pragma unroll
             for (int a = 0; a < 3; a++) {
                 cb[a] = (fb[a] >> 1) + d[a];
-                ok = ok && (!d[a] || (fb[a] & 1)) && cb[a] < nbc && 8 * cb[a] <= ((e[a] >> level) >> 1);
+                ok = ok && (!d[a] || (fb[a] & 1)) && cb[a] < nbc && 8 * cb[a] <= st_rule_omax(e[a], level);
             }
             if (ok) Lc.p[(int64_t)b * Lc.mt + bk_morton(cb[0], cb[1], cb[2])] = 1u;
         }
@@ -287,7 +282,7 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_coarse_stencil(BkLevel Lf, BkLe
         const int b = (int)(t >> (3 * Lc.mb));
         const int cb[3] = {(int)bk_compact3(mc >> 2), (int)bk_compact3(mc >> 1), (int)bk_compact3(mc)};
         const int* e = st->ext[blk_seg ? blk_seg[b] : 0];
-        const int omax[3] = {(e[0] >> level) >> 1, (e[1] >> level) >> 1, (e[2] >> level) >> 1};
+        const int omax[3] = {st_rule_omax(e[0], level), st_rule_omax(e[1], level), st_rule_omax(e[2], level)};
         const int oz = 8 * cb[0] + w;
         unsigned long long word = 0ull;
         if (oz <= omax[0]) {
@@ -366,7 +361,6 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_emit(BkLevel L, int32_t* coords
 
 // both tables of the strided pair set: nbr_up[k][i] = coarse row reached from fine row i through offset k, nbr_down[k][r] = i
 // (every (k, r) has one writer; the rest keeps the -1 it was filled with); class histogram of the fine rows for the parity order
-__device__ __forceinline__ int bk_parity_class(int z, int y, int x) { return ((z & 1) << 2) | ((y & 1) << 1) | (x & 1); }
 __global__ void __launch_bounds__(BK_BLOCK) k_bk_updown(const int32_t* coords, const int64_t* n_dev, int64_t cap_f, BkLevel Lc, const BkState* st,
                                                         int level, const int32_t* blk_seg, const int64_t* m_dev, int64_t cap_c,
                                                         int32_t* nbr_up, int32_t* nbr_down, uint32_t* parity_count) {
@@ -380,9 +374,9 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_updown(const int32_t* coords, c
         const int4 c4 = reinterpret_cast<const int4*>(coords)[i];
         const int b = c4.x, c[3] = {c4.y, c4.z, c4.w};
         const int* e = st->ext[blk_seg ? blk_seg[b] : 0];
-        const int omax[3] = {(e[0] >> level) >> 1, (e[1] >> level) >> 1, (e[2] >> level) >> 1};
-        atomicAdd(&hist[bk_parity_class(c[0], c[1], c[2])], 1u);
-        // a fine voxel reaches at most 2 x 2 x 2 outputs (o = c >> 1, and o + 1 when c is odd), nearly always in ONE coarse brick:
+        const int omax[3] = {st_rule_omax(e[0], level), st_rule_omax(e[1], level), st_rule_omax(e[2], level)};
+        atomicAdd(&hist[st_rule_parity_class(c[0], c[1], c[2])], 1u);
+        // a fine voxel reaches at most 2 x 2 x 2 outputs, nearly always in ONE coarse brick:
         // the brick's table entry and the mask word of a z plane are fetched when they change, not once per offset
         int64_t t_have = -1;
         int slot = -1, w_have = -1;
@@ -394,10 +388,9 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_updown(const int32_t* coords, c
 #pragma unroll
             for (int j = 0; j < 9; j++) {
                 const int k = kz * 9 + j;
-                const int nz = c[0] + 1 - kz, ny = c[1] + 1 - j / 3, nx = c[2] + 1 - j % 3;
-                int r = -1;
-                if (!((nz | ny | nx) & 1) && nz >= 0 && ny >= 0 && nx >= 0 && (nz >> 1) <= omax[0] && (ny >> 1) <= omax[1] && (nx >> 1) <= omax[2]) {
-                    const int oz = nz >> 1, oy = ny >> 1, ox = nx >> 1;
+                int r = -1, o[3];
+                if (st_rule_out(c, k, omax, o)) {
+                    const int oz = o[0], oy = o[1], ox = o[2];
                     if (oz < limc && oy < limc && ox < limc) {
                         const int64_t tc = bk_tab(Lc, b, oz, oy, ox);
                         if (tc != t_have) {
@@ -423,52 +416,6 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_updown(const int32_t* coords, c
     if (threadIdx.x < 8 && hist[threadIdx.x]) atomicAdd(&parity_count[threadIdx.x], hist[threadIdx.x]);
 }
 
-// order[p] = fine row | (8 + class) << 28, rows grouped by coordinate parity class (see rulebook.hip k_rb_parity_order: the
-// launch order of the inverse convolution; never changes a result).  count[8] from k_bk_updown, cursor[8] zeroed.
-#define BK_ORDER_BLOCKS 512
-__global__ void __launch_bounds__(BK_BLOCK) k_bk_parity_order(const int32_t* coords, const int64_t* n_dev, int64_t cap, const uint32_t* count,
-                                                              uint32_t* cursor, int32_t* order, const BkState* st) {
-    __shared__ uint32_t hist[8], gbase[8], lcur[8];
-    if (st->fail) return;
-    const int64_t n = *n_dev < cap ? *n_dev : cap;
-    const int lane = threadIdx.x & 63;
-    const int64_t per = (n + gridDim.x - 1) / gridDim.x, chunk = (per + BK_BLOCK - 1) / BK_BLOCK * BK_BLOCK;
-    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
-    if (threadIdx.x < 8) { hist[threadIdx.x] = 0; lcur[threadIdx.x] = 0; }
-    __syncthreads();
-    for (int64_t i0 = lo + (threadIdx.x - lane); i0 < hi; i0 += BK_BLOCK) {
-        const int64_t i = i0 + lane;
-        int cls = -1;
-        if (i < hi) cls = bk_parity_class(coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]);
-        for (int q = 0; q < 8; q++) {
-            const unsigned long long mask = __ballot(cls == q);
-            if (mask != 0ull && lane == __ffsll((long long)mask) - 1) atomicAdd(&hist[q], (uint32_t)__popcll(mask));
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        uint32_t base = 0;
-        for (int q = 0; q < (int)threadIdx.x; q++) base += count[q];
-        gbase[threadIdx.x] = base + (hist[threadIdx.x] ? atomicAdd(&cursor[threadIdx.x], hist[threadIdx.x]) : 0u);
-    }
-    __syncthreads();
-    for (int64_t i0 = lo + (threadIdx.x - lane); i0 < hi; i0 += BK_BLOCK) {
-        const int64_t i = i0 + lane;
-        int cls = -1;
-        if (i < hi) cls = bk_parity_class(coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]);
-        for (int q = 0; q < 8; q++) {
-            const unsigned long long mask = __ballot(cls == q);
-            if (mask == 0ull) continue;
-            const int leader = __ffsll((long long)mask) - 1;
-            uint32_t at = 0;
-            if (lane == leader) at = atomicAdd(&lcur[q], (uint32_t)__popcll(mask));
-            at = __shfl(at, leader);
-            if (cls == q)
-                order[gbase[q] + at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)((uint32_t)i | ((8u + (uint32_t)q) << 28));
-        }
-    }
-}
-
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 struct BkPlan {
     int depth;
@@ -488,6 +435,8 @@ static bool bk_plan(int64_t n0, int n_blocks, int coord_bound, int depth, const 
         P->ntab[l] = (int64_t)n_blocks << (3 * mb);
         if (P->ntab[l] >= (1ll << 31)) return false;  // tidx is 32 bit
         const int64_t cap = l == 0 ? n0 : caps[l];
+        // the level's row capacity (level 0: caps[0], which may exceed n0) must fit the tagged row order
+        if ((l == 0 && caps && caps[0] > cap ? caps[0] : cap) >= ST_RULE_ROW_LIMIT) return false;
         P->slot_cap[l] = cap < P->ntab[l] ? cap : P->ntab[l];
         bound = (bound - 1) / 2 + 1;
     }
@@ -600,9 +549,7 @@ extern "C" int st_brick_pyramid(const int32_t* coords0, int64_t n0, int n_blocks
         (void)hipMemsetAsync(pc, 0, 16 * sizeof(uint32_t), stream);
         hipLaunchKernelGGL(k_bk_updown, dim3(bk_grid(cap)), dim3(BK_BLOCK), 0, stream, (const int32_t*)coords_out[l], (const int64_t*)L[l].n_vox, cap,
                            L[l + 1], (const BkState*)Y.st, l, blk_seg, (const int64_t*)L[l + 1].n_vox, cap_c, up[l], down[l], pc);
-        const unsigned og = bk_grid(cap) < BK_ORDER_BLOCKS ? bk_grid(cap) : BK_ORDER_BLOCKS;
-        hipLaunchKernelGGL(k_bk_parity_order, dim3(og), dim3(BK_BLOCK), 0, stream, (const int32_t*)coords_out[l], (const int64_t*)L[l].n_vox, cap,
-                           (const uint32_t*)pc, pc + 8, up_order[l], (const BkState*)Y.st);
+        st_rule_parity_order(coords_out[l], cap, L[l].n_vox, &Y.st->fail, pc, up_order[l], stream);
     }
     // the ONE read-back: rows per level + the fail flags
     struct { int64_t counts[2 * (BK_MAX_DEPTH + 1)]; } hc;

@@ -6,15 +6,12 @@
 // indice_key 1..3 by SparseConv3d, :58-67, and re-used by SparseInverseConv3d, :91-98).
 // Here each level's tables are built once and shared by every conv of that level.
 //
-// All tables are OUTPUT-stationary: nbr[k * n_out + o] = input row feeding output row o through
-// kernel offset k (k = (kz*3+ky)*3+kx), or -1.  Orientation follows the oracle
-// (oracle/unet_oracle.py): subm  in = out + (k-1);  strided (k3,s2,p1)  in = 2*out - 1 + k;
-// inverse: the strided pairs with roles swapped, same k.
-// The strided output set is emitted in canonical first-appearance order (inputs in row order,
-// k ascending) via hash insert with atomicMin(candidate id) + ordered compaction -- no sort, no
-// atomics-order dependence, bit-reproducible.
+// What the tables mean (offsets, orientation, the strided rule, the tagged row order): st_rule.h.  The strided output set is
+// emitted in canonical first-appearance order (inputs in row order, k ascending) via hash insert with atomicMin(candidate id)
+// + ordered compaction -- no sort, no atomics-order dependence, bit-reproducible.
 #include "st_common.h"
 #include "st_grid.h"  // ST_MAX_SEG
+#include "st_rule.h"
 
 #define RB_BLOCK 256
 
@@ -53,9 +50,7 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_subm(const int32_t* coords, int
     }
 }
 
-// The spatial extent that clips the strided output set is the extent of the voxel's own CLOUD: a one-cloud call has one
-// extent for the whole batch of blocks (DESIGN.md "canonical choices"); a batched call keeps one per cloud (blk_seg maps
-// the block index coords[:,0] to its cloud), so a cloud's coarse sets do not depend on what else is in the batch.
+// One extent per cloud (blk_seg maps the block index coords[:,0] to its cloud; DESIGN.md "canonical choices")
 struct RbState {
     int ext[ST_MAX_SEG][3];  // max coordinate per axis (z,y,x) over the blocks of each cloud
     uint32_t n_out;
@@ -70,20 +65,13 @@ __global__ void k_rb_state_init(RbState* st) {
 __global__ void __launch_bounds__(RB_BLOCK) k_rb_extent(const int32_t* coords, int64_t n, RbState* st, const int32_t* blk_seg,
                                                         int nseg) {
     __shared__ int m[ST_MAX_SEG * 3];
-    for (int i = threadIdx.x; i < nseg * 3; i += blockDim.x) m[i] = 0;
-    __syncthreads();
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int s = blk_seg ? blk_seg[coords[4 * i]] : 0;
-        for (int a = 0; a < 3; a++) {
-            int c = coords[4 * i + 1 + a];
-            if (c > m[3 * s + a]) atomicMax(&m[3 * s + a], c);
-        }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nseg * 3; i += blockDim.x) if (m[i]) atomicMax(&(&st->ext[0][0])[i], m[i]);
+    st_ext_clear(m, nseg);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        st_ext_offer(m, blk_seg ? blk_seg[coords[4 * i]] : 0, coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]);
+    st_ext_flush(m, nseg, &st->ext[0][0]);
 }
 
-// candidate outputs of input voxel i: o = (c + 1 - k) / 2 per axis when even and inside out_shape
+// candidate outputs of input voxel i: st_rule_out over the 27 offsets
 // PASS 0: insert(o -> min candidate id i*27+k); PASS 1: count the candidates that won and remember which (bit k of
 // win[i]); PASS 2: emit rows from that mask (no hash access).  Passes 1 and 2 do nothing once pass 0 has flagged a full
 // table (the host sees the flag after pass 2 and retries with a larger capacity).
@@ -93,13 +81,13 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_down_pass(const int32_t* coords
                                                            uint32_t* cnt_or_off, uint32_t* win, int32_t* out_coords,
                                                            int64_t max_out, const int32_t* blk_seg) {
     if (PASS != 0 && st->fail) return;
-    int oshape[3];
-    for (int a = 0; a < 3; a++) oshape[a] = st->ext[0][a] / 2 + 1;  // ((ext+1) - 1)/2 + 1
+    int omax[3], o[3];
+    for (int a = 0; a < 3; a++) omax[a] = st_rule_omax(st->ext[0][a]);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         uint32_t mine = 0, won = PASS == 2 ? win[i] : 0u;
         if (PASS == 2 && won == 0u) continue;
         int b = coords[4 * i], c[3] = {coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]};
-        if (blk_seg) { const int* e = st->ext[blk_seg[b]]; for (int a = 0; a < 3; a++) oshape[a] = e[a] / 2 + 1; }
+        if (blk_seg) { const int* e = st->ext[blk_seg[b]]; for (int a = 0; a < 3; a++) omax[a] = st_rule_omax(e[a]); }
         uint32_t off = PASS == 2 ? cnt_or_off[i] : 0u;
         if (PASS == 1) {  // which of my candidates is the stored winner: nine overlapped look-ups per z-plane
 #pragma unroll
@@ -109,10 +97,8 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_down_pass(const int32_t* coords
                 int r[9];
 #pragma unroll
                 for (int j = 0; j < 9; j++) {
-                    const int nz = c[0] + 1 - kz, ny = c[1] + 1 - j / 3, nx = c[2] + 1 - j % 3;
-                    const int oz = nz >> 1, oy = ny >> 1, ox = nx >> 1;
-                    valid[j] = !((nz | ny | nx) & 1) && nz >= 0 && ny >= 0 && nx >= 0 && oz < oshape[0] && oy < oshape[1] && ox < oshape[2];
-                    key[j] = st_pack_key(b, oz, oy, ox);
+                    valid[j] = st_rule_out(c, kz, j / 3, j % 3, omax, o);
+                    key[j] = st_pack_key(b, o[0], o[1], o[2]);
                 }
                 st_hash_find_batch<9>(keys, vals, cap, key, valid, r);
 #pragma unroll
@@ -128,23 +114,19 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_down_pass(const int32_t* coords
             for (int ky = 0; ky < 3; ky++)
                 for (int kx = 0; kx < 3; kx++, k++) {
                     if (PASS == 2 && !((won >> k) & 1u)) continue;
-                    int nz = c[0] + 1 - kz, ny = c[1] + 1 - ky, nx = c[2] + 1 - kx;
-                    if ((nz | ny | nx) & 1) continue;
-                    if (nz < 0 || ny < 0 || nx < 0) continue;
-                    int oz = nz >> 1, oy = ny >> 1, ox = nx >> 1;
-                    if (oz >= oshape[0] || oy >= oshape[1] || ox >= oshape[2]) continue;
+                    if (!st_rule_out(c, kz, ky, kx, omax, o)) continue;
                     if (PASS == 2) {
                         uint32_t row = off + mine;
                         if ((int64_t)row < max_out) {
                             out_coords[4 * row] = b;
-                            out_coords[4 * row + 1] = oz;
-                            out_coords[4 * row + 2] = oy;
-                            out_coords[4 * row + 3] = ox;
+                            out_coords[4 * row + 1] = o[0];
+                            out_coords[4 * row + 2] = o[1];
+                            out_coords[4 * row + 3] = o[2];
                         }
                         mine++;
                         continue;
                     }
-                    unsigned long long key = st_pack_key(b, oz, oy, ox);
+                    unsigned long long key = st_pack_key(b, o[0], o[1], o[2]);
                     unsigned cand = (unsigned)(i * 27 + k);
                     // ~6 fine voxels offer themselves for every coarse one: look before touching the slot with atomics
                     if (!st_hash_insert_min_dup(keys, vals, cap, key, cand, &st->fail, 1u)) atomicOr(&st->fail, 1u);
@@ -163,27 +145,21 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_relabel(const int32_t* out_coor
     }
 }
 
-struct RbShape { int v[3]; };
-
-// parity class of a fine voxel: which of the 27 offsets of the strided pair set can have a partner depends only on it
-// (per axis an even coordinate pairs through k = 1, an odd one through k = 0 and k = 2): 1, 2, 4 or 8 live offsets.
-__device__ __forceinline__ int rb_parity_class(const int* c) { return ((c[0] & 1) << 2) | ((c[1] & 1) << 1) | (c[2] & 1); }
-
 // Both tables of the strided pair set from ONE round of look-ups: fine voxel i reaches coarse row r through offset k
 // (nbr_up[k][i] = r), and that same pair read from the coarse side is nbr_down[k][r] = i -- (k, r) determines the fine
 // coordinate 2*o - 1 + k, so every entry of nbr_down has exactly one writer; the rest keeps the -1 it was filled with.
-__global__ void __launch_bounds__(RB_BLOCK) k_rb_up_nbr(const int32_t* coords, int64_t n, RbShape osh,
+__global__ void __launch_bounds__(RB_BLOCK) k_rb_up_nbr(const int32_t* coords, int64_t n, int ext_z, int ext_y, int ext_x,
                                                         const unsigned long long* ckeys, const unsigned* cvals,
                                                         unsigned long long ccap, int32_t* nbr, int32_t* nbr_down, int64_t m,
                                                         uint32_t* parity_count, const int32_t* blk_seg, const int32_t* ext_dev) {
     __shared__ uint32_t hist[8];
     if (threadIdx.x < 8) hist[threadIdx.x] = 0;
     __syncthreads();
-    int oshape[3] = {osh.v[0], osh.v[1], osh.v[2]};
+    int omax[3] = {st_rule_omax(ext_z), st_rule_omax(ext_y), st_rule_omax(ext_x)}, o[3];  // one cloud: the host's extent
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         int b = coords[4 * i], c[3] = {coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]};
-        if (blk_seg) { const int32_t* e = ext_dev + 3 * blk_seg[b]; for (int a = 0; a < 3; a++) oshape[a] = e[a] / 2 + 1; }
-        if (parity_count) atomicAdd(&hist[rb_parity_class(c)], 1u);
+        if (blk_seg) { const int32_t* e = ext_dev + 3 * blk_seg[b]; for (int a = 0; a < 3; a++) omax[a] = st_rule_omax(e[a]); }
+        if (parity_count) atomicAdd(&hist[st_rule_parity_class(c[0], c[1], c[2])], 1u);
 #pragma unroll
         for (int kz = 0; kz < 3; kz++) {  // nine offsets per batch of overlapped look-ups (at most four of them live)
             unsigned long long key[9];
@@ -191,10 +167,8 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_up_nbr(const int32_t* coords, i
             int r[9];
 #pragma unroll
             for (int j = 0; j < 9; j++) {
-                const int nz = c[0] + 1 - kz, ny = c[1] + 1 - j / 3, nx = c[2] + 1 - j % 3;
-                const int oz = nz >> 1, oy = ny >> 1, ox = nx >> 1;
-                valid[j] = !((nz | ny | nx) & 1) && nz >= 0 && ny >= 0 && nx >= 0 && oz < oshape[0] && oy < oshape[1] && ox < oshape[2];
-                key[j] = st_pack_key(b, oz, oy, ox);
+                valid[j] = st_rule_out(c, kz, j / 3, j % 3, omax, o);
+                key[j] = st_pack_key(b, o[0], o[1], o[2]);
             }
             st_hash_find_batch<9>(ckeys, cvals, ccap, key, valid, r);
 #pragma unroll
@@ -209,16 +183,17 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_up_nbr(const int32_t* coords, i
     if (parity_count && threadIdx.x < 8 && hist[threadIdx.x]) atomicAdd(&parity_count[threadIdx.x], hist[threadIdx.x]);
 }
 
-// order[p] = fine row | (8 + class) << 28, rows grouped by parity class (class-major; inside a class in whatever order the
-// workgroups reach the cursors -- the convolution's result does not depend on it, see st_sparse_conv_fwd; the tag in
-// the top four bits tells the conv kernel which offsets can be live for the row).  count[8] from k_rb_up_nbr, cursor[8]
-// zeroed.  A workgroup owns a contiguous chunk of rows: it counts its chunk, reserves one range per class with ONE global
-// atomic each (a few thousand atomics on eight words instead of one per wavefront and class), then deals the rows out
-// through cursors in LDS.
+// The tagged row order of st_rule.h: rows grouped by parity class (class-major; inside a class in whatever order the
+// workgroups reach the cursors -- the convolution's result does not depend on it, see st_sparse_conv_fwd).  A workgroup
+// owns a contiguous chunk of rows: it counts its chunk, reserves one range per class with ONE global atomic each (a few
+// thousand atomics on eight words instead of one per wavefront and class), then deals the rows out through cursors in LDS.
 #define RB_ORDER_BLOCKS 512
-__global__ void __launch_bounds__(RB_BLOCK) k_rb_parity_order(const int32_t* coords, int64_t n, const uint32_t* count,
-                                                              uint32_t* cursor, int32_t* order) {
+__global__ void __launch_bounds__(RB_BLOCK) k_rb_parity_order(const int32_t* coords, int64_t cap, const int64_t* n_dev,
+                                                              const unsigned* fail, const uint32_t* count, uint32_t* cursor,
+                                                              int32_t* order) {
     __shared__ uint32_t hist[8], gbase[8], lcur[8];
+    if (fail && *fail) return;
+    const int64_t n = n_dev && *n_dev < cap ? *n_dev : cap;
     const int lane = threadIdx.x & 63;
     const int64_t per = (n + gridDim.x - 1) / gridDim.x, chunk = (per + RB_BLOCK - 1) / RB_BLOCK * RB_BLOCK;
     const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
@@ -227,7 +202,7 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_parity_order(const int32_t* coo
     for (int64_t i0 = lo + (threadIdx.x - lane); i0 < hi; i0 += RB_BLOCK) {
         const int64_t i = i0 + lane;
         int cls = -1;
-        if (i < hi) { const int c[3] = {coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]}; cls = rb_parity_class(c); }
+        if (i < hi) cls = st_rule_parity_class(coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]);
         for (int q = 0; q < 8; q++) {
             const unsigned long long mask = __ballot(cls == q);
             if (mask != 0ull && lane == __ffsll((long long)mask) - 1) atomicAdd(&hist[q], (uint32_t)__popcll(mask));
@@ -243,7 +218,7 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_parity_order(const int32_t* coo
     for (int64_t i0 = lo + (threadIdx.x - lane); i0 < hi; i0 += RB_BLOCK) {
         const int64_t i = i0 + lane;
         int cls = -1;
-        if (i < hi) { const int c[3] = {coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]}; cls = rb_parity_class(c); }
+        if (i < hi) cls = st_rule_parity_class(coords[4 * i + 1], coords[4 * i + 2], coords[4 * i + 3]);
         for (int q = 0; q < 8; q++) {
             const unsigned long long mask = __ballot(cls == q);
             if (mask == 0ull) continue;
@@ -252,9 +227,15 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_parity_order(const int32_t* coo
             if (lane == leader) at = atomicAdd(&lcur[q], (uint32_t)__popcll(mask));
             at = __shfl(at, leader);
             if (cls == q)
-                order[gbase[q] + at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = (int32_t)((uint32_t)i | ((8u + (uint32_t)q) << 28));
+                order[gbase[q] + at + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = st_rule_tag(i, q);
         }
     }
+}
+
+void st_rule_parity_order(const int32_t* coords, int64_t cap, const int64_t* n_dev, const unsigned* fail, uint32_t* pc, int32_t* order,
+                          hipStream_t stream) {
+    const unsigned g = rb_grid(cap) < RB_ORDER_BLOCKS ? rb_grid(cap) : RB_ORDER_BLOCKS;
+    hipLaunchKernelGGL(k_rb_parity_order, dim3(g), dim3(RB_BLOCK), 0, stream, coords, cap, n_dev, fail, (const uint32_t*)pc, pc + 8, order);
 }
 
 extern "C" int64_t st_hash_capacity(int64_t n) { return st_next_pow2(2 * (n > 8 ? n : 8)); }
@@ -362,8 +343,7 @@ extern "C" int st_build_strided_outputs(const int32_t* coords, int64_t n, int64_
 }
 
 // Phase 2: the two neighbour tables of the pair set: nbr_down [27][n_out] (fine rows), nbr_up [27][n] (coarse rows);
-// up_order (optional, n + 16 words: the tail is scratch): the fine rows grouped by coordinate parity and tagged with
-// their class, the row order the inverse convolution should be launched with (st_sparse_conv_fwd's row_order).
+// up_order (optional, n + 16 words: the tail is scratch): the tagged row order for st_sparse_conv_fwd's row_order.
 // Batched form: blk_seg / ext_dev as given to / filled by st_build_strided_outputs_seg (NULL: one cloud, extent_host).
 extern "C" int st_build_strided_rulebook_seg(const int32_t* coords, int64_t n, const unsigned long long* fkeys,
                                          const unsigned* fvals, int64_t fcap, const int32_t* out_coords, int64_t n_out,
@@ -374,18 +354,14 @@ extern "C" int st_build_strided_rulebook_seg(const int32_t* coords, int64_t n, c
     hipStream_t stream = (hipStream_t)stream_;
     if (n == 0) return ST_OK;
     ST_REQUIRE((blk_seg == nullptr) == (ext_dev == nullptr), "strided: blk_seg and ext_dev go together");
-    ST_REQUIRE(up_order == nullptr || n < (1ll << 28), "strided: the tagged row order holds at most 2^28 rows");
-    RbShape osh;
-    for (int a = 0; a < 3; a++) osh.v[a] = extent_host[a] / 2 + 1;
+    ST_REQUIRE(up_order == nullptr || n < ST_RULE_ROW_LIMIT, "strided: the tagged row order holds at most 2^28 rows");
     (void)fkeys; (void)fvals; (void)fcap;  // the fine hash is no longer consulted (kept in the signature)
     if (n_out) (void)hipMemsetAsync(nbr_down, 0xff, 27 * n_out * sizeof(int32_t), stream);
     uint32_t* pc = up_order ? reinterpret_cast<uint32_t*>(up_order + n) : nullptr;  // 8 class counts + 8 cursors
     if (pc) (void)hipMemsetAsync(pc, 0, 16 * sizeof(uint32_t), stream);
-    hipLaunchKernelGGL(k_rb_up_nbr, dim3(rb_grid(n)), dim3(RB_BLOCK), 0, stream, coords, n, osh, ckeys, cvals,
-                       (unsigned long long)ccap, nbr_up, nbr_down, n_out, pc, blk_seg, ext_dev);
-    if (pc)
-        hipLaunchKernelGGL(k_rb_parity_order, dim3(rb_grid(n) < RB_ORDER_BLOCKS ? rb_grid(n) : RB_ORDER_BLOCKS), dim3(RB_BLOCK), 0, stream, coords,
-                           n, (const uint32_t*)pc, pc + 8, up_order);
+    hipLaunchKernelGGL(k_rb_up_nbr, dim3(rb_grid(n)), dim3(RB_BLOCK), 0, stream, coords, n, extent_host[0], extent_host[1],
+                       extent_host[2], ckeys, cvals, (unsigned long long)ccap, nbr_up, nbr_down, n_out, pc, blk_seg, ext_dev);
+    if (pc) st_rule_parity_order(coords, n, nullptr, nullptr, pc, up_order, stream);
     ST_CHECK_LAUNCH();
     return ST_OK;
 }

@@ -14,6 +14,7 @@
 // Weights are pre-laid out [K][Cin][Cout]; a workgroup handles ONE cout tile, so every weight
 // address is wave-uniform and the compiler feeds the FMAs from scalar loads (SGPR operands).
 #include "st_common.h"
+#include "st_rule.h"  // row_order entries: row, parity tag, live offsets
 
 #define CONV_BLOCK 256
 
@@ -31,22 +32,6 @@ __device__ __forceinline__ void conv_store4(st_h* p, float a, float b, float c, 
     *reinterpret_cast<st_v4h*>(p) = st_v4h{(st_h)a, (st_h)b, (st_h)c, (st_h)d};  // round to nearest even
 }
 
-// row_order entries: bits 0-27 = output row.  Top four bits 0 = nothing known; 8 + c = the row belongs to coordinate
-// parity class c = (z&1)<<2 | (y&1)<<1 | (x&1) of an inverse k3-s2-p1 convolution: per axis an even coordinate pairs
-// through k = 1 only, an odd one through k = 0 and 2, so at most 8 of the 27 table entries can be >= 0 and the rest
-// need not be read.  Returns the 27-bit mask of offsets worth reading.
-__device__ __forceinline__ uint32_t conv_live_offsets(int32_t entry, int K) {
-    const uint32_t tag = (uint32_t)entry >> 28;
-    if (!(tag & 8u) || K != 27) return 0xffffffffu;
-    const uint32_t ax[3] = {(tag & 4u) ? 5u : 2u, (tag & 2u) ? 5u : 2u, (tag & 1u) ? 5u : 2u};  // z, y, x: {0,2} or {1}
-    uint32_t live = 0;
-#pragma unroll
-    for (int k = 0; k < 27; k++)
-        if (((ax[0] >> (k / 9)) & (ax[1] >> ((k / 3) % 3)) & (ax[2] >> (k % 3))) & 1u) live |= 1u << k;
-    return live;
-}
-#define CONV_ROW_MASK 0x0fffffff
-
 template <int CIN, int COT, class TIN = float, class TOUT = float>
 __global__ void __launch_bounds__(CONV_BLOCK) k_sparse_conv(const TIN* __restrict__ x0, int c0,
                                                             const TIN* __restrict__ x1, const int32_t* __restrict__ nbr,
@@ -60,8 +45,8 @@ __global__ void __launch_bounds__(CONV_BLOCK) k_sparse_conv(const TIN* __restric
     const bool active = pos < n_out;
     // row_order (optional): the output rows in an order that makes the live offsets wave-uniform (see st_sparse_conv_fwd)
     const int32_t entry = active && row_order ? row_order[pos] : 0;
-    const int64_t o = active && row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos;
-    const uint32_t live = conv_live_offsets(entry, K);
+    const int64_t o = active && row_order ? (int64_t)st_rule_row(entry) : pos;
+    const uint32_t live = st_rule_live_offsets(entry, K);
     const int c1 = CIN - c0;
     float acc[COT];
 #pragma unroll
@@ -160,8 +145,8 @@ __global__ void __launch_bounds__(CONV_BLOCK) k_sparse_conv_any(const float* __r
     if (pos >= n_out) return;
     const int co0 = (int)blockIdx.y * 4, nco = cout - co0 < 4 ? cout - co0 : 4;
     const int32_t entry = row_order ? row_order[pos] : 0;
-    const int64_t o = row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos;
-    const uint32_t live = conv_live_offsets(entry, K);
+    const int64_t o = row_order ? (int64_t)st_rule_row(entry) : pos;
+    const uint32_t live = st_rule_live_offsets(entry, K);
     const int c1 = cin - c0;
     float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int k = 0; k < K; k++) {
@@ -371,8 +356,8 @@ __device__ __forceinline__ void conv_rule_gemm(MF_PARAMS(typename OP::T, typenam
     for (int t = 0; t < RT; t++) {
         const int64_t pos = obase + t * 16 + i16;
         const int32_t entry = pos < n_out && row_order ? row_order[pos] : 0;
-        orow[t] = pos < n_out ? (row_order ? (int64_t)(entry & CONV_ROW_MASK) : pos) : -1;
-        live[t] = conv_live_offsets(entry, K);
+        orow[t] = pos < n_out ? (row_order ? (int64_t)st_rule_row(entry) : pos) : -1;
+        live[t] = st_rule_live_offsets(entry, K);
     }
     for (int j = 0; (PAIR ? 2 * j : j) < K; j++) {
         const int k = PAIR ? 2 * j + (g >> 1) : j;  // this lane's offset (of the pair)
@@ -421,7 +406,7 @@ __device__ __forceinline__ void conv_rule_gemm(MF_PARAMS(typename OP::T, typenam
             for (int r = 0; r < 4; r++) {
                 const int64_t pos = obase + t * 16 + g * 4 + r;
                 if (pos >= n_out) continue;
-                const int64_t o = row_order ? (int64_t)(row_order[pos] & CONV_ROW_MASK) : pos;
+                const int64_t o = row_order ? (int64_t)st_rule_row(row_order[pos]) : pos;
                 float v = acc[t][ct][r];
                 if (scale) v = fmaf(v, sc, sh);
                 if (residual) v += (float)residual[o * COUT + ch];
@@ -586,7 +571,7 @@ extern "C" int st_sparse_conv_mfma_fwd(const float* x0, int c0, const float* x1,
 // nbr [K][n_out] or NULL (K must be 1: pointwise); scale/shift/residual may be NULL.  nbr_stride: elements between the rows of
 // the table (0 = n_out; st_brick_pyramid lays its tables out with the level's capacity as the stride).
 // row_order (may be NULL): a permutation of the output rows (bits 0-27; the top four bits may carry the parity tag
-// described at conv_live_offsets, 0 = none); wave / tile position p works on output row_order[p].
+// described at st_rule_live_offsets, 0 = none); wave / tile position p works on output row_order[p].
 // Every row is still computed by one lane (or one MFMA tile row) with the same k-ordered arithmetic, so the result
 // does not depend on it -- it only decides which rows share a wavefront.  The inverse ("up") convs pass the fine
 // rows grouped by coordinate parity (st_build_strided_rulebook): inside a parity class only 1, 2, 4 or 8 of the 27

@@ -1,4 +1,5 @@
 """Rulebooks (bit-exact) and network outputs (fp32 tolerance) of the HIP path vs oracle/unet_oracle.py."""
+import ctypes
 from pathlib import Path
 
 import numpy as np
@@ -7,6 +8,7 @@ import torch
 
 from oracle import unet_oracle as uo
 from oracle import voxel_oracle as vo
+from smart_tree_amd import _lib
 from smart_tree_amd.model import sparse_ops as ops
 from smart_tree_amd.model.model import Smart_Tree
 from smart_tree_amd.model.sparse import sparse_from_batch
@@ -374,10 +376,12 @@ def _renumber(table, perm_out, perm_in, n_ref_out):
     return out
 
 
-@pytest.mark.parametrize("case", ["tree", "isolated-odd", "batch"])
-def test_brick_pyramid_matches_the_oracle(backend, case):
+@pytest.mark.parametrize("case,builder", [pytest.param(c, b, id=c if b == "brick" else f"{c}-{b}")
+                                          for c in ("tree", "isolated-odd", "batch", "faces") for b in ("brick", "hash")])
+def test_brick_pyramid_matches_the_oracle(backend, case, builder):
     """Every level's active set, submanifold table, strided and inverse tables equal the oracle's after renumbering the rows
-    (brick order instead of first appearance); level 0's order0 is the permutation that produces its coordinates."""
+    (brick order instead of first appearance); level 0's order0 is the permutation that produces its coordinates.  The hash-table
+    builders (`builder == "hash"`) face the same inputs: everything but order0, which they do not have."""
     blk_seg, n_seg = None, 1
     if case == "tree":
         coords = _small_batch()["coords"]
@@ -386,6 +390,14 @@ def test_brick_pyramid_matches_the_oracle(backend, case):
         z, y, x = np.meshgrid(g, g, g, indexing="ij")
         coords = np.stack([np.zeros(z.size, np.int32), z.ravel(), y.ravel(), x.ravel()], axis=1).astype(np.int32)
         coords = np.repeat(coords, 1, axis=0)
+    elif case == "faces":  # every branch of the strided rule at the smallest size: coordinate 0, both faces of a brick, an even
+        # extent (cloud 0: 16) and an odd one (cloud 1: 15, the clip removes the outputs at o = 8)
+        grid = lambda v: np.stack(np.meshgrid(v, v, v, indexing="ij"), axis=-1).reshape(-1, 3)
+        a, b = grid(np.array([0, 7, 8, 15, 16])), grid(np.array([0, 1, 7, 8, 15]))
+        coords = np.concatenate([np.concatenate([np.full((len(c), 1), i), c], axis=1) for i, c in enumerate((a, b))]).astype(np.int32)
+        assert len(coords) == 250
+        seg = np.array([0, 1], np.int32)
+        blk_seg, n_seg = torch.from_numpy(seg).to(backend), 2
     else:  # two clouds in one batch: each cloud's coarse sets are clipped to ITS extent
         a, b = _small_batch(seed=5)["coords"], _small_batch(n=3000, seed=7)["coords"]
         b = b.copy()
@@ -396,12 +408,15 @@ def test_brick_pyramid_matches_the_oracle(backend, case):
     rng = np.random.RandomState(0)
     coords = coords[rng.permutation(len(coords))]  # any input order
     nb, bound = _hint(coords)
-    got = ops.brick_pyramid(torch.from_numpy(coords).to(backend), 3, nb, bound, blk_seg, n_seg)
-    assert got is not None
-    pyr, order0 = got
-    order0 = order0.cpu().numpy()
-    assert sorted(order0.tolist()) == list(range(len(coords)))
-    np.testing.assert_array_equal(pyr.coords[0].cpu().numpy(), coords[order0])
+    if builder == "hash":
+        pyr = ops.build_pyramid(torch.from_numpy(coords).to(backend), 3, blk_seg, n_seg)
+    else:
+        got = ops.brick_pyramid(torch.from_numpy(coords).to(backend), 3, nb, bound, blk_seg, n_seg)
+        assert got is not None
+        pyr, order0 = got
+        order0 = order0.cpu().numpy()
+        assert sorted(order0.tolist()) == list(range(len(coords)))
+        np.testing.assert_array_equal(pyr.coords[0].cpu().numpy(), coords[order0])
     if n_seg == 1:
         ref_levels = [coords]
         for _ in range(3):
@@ -413,6 +428,8 @@ def test_brick_pyramid_matches_the_oracle(backend, case):
             for _ in range(3):
                 per[s].append(uo.strided_out_coords(per[s][-1]))
         ref_levels = [np.concatenate([per[0][l], per[1][l]]) for l in range(4)]
+        if case == "faces":
+            assert per[0][1][:, 1:].max() == 8 and per[1][1][:, 1:].max() == 7, "the case no longer exercises the clip"
     perms = []
     for level in range(4):
         mine = pyr.coords[level].cpu().numpy()
@@ -439,6 +456,20 @@ def test_brick_pyramid_matches_the_oracle(backend, case):
         cls = ((c[:, 1] & 1) << 2) | ((c[:, 2] & 1) << 1) | (c[:, 3] & 1)
         assert (np.diff(cls) >= 0).all()
         np.testing.assert_array_equal((tagged >> 28) & 0xF, 8 + cls)
+
+
+def test_a_level_of_2_to_the_28_rows_is_refused_on_the_host(backend):
+    """A tagged row order (csrc/st_rule.h) keeps 28 bits for the row.  The brick pyramid cannot be sized for a level of that
+    capacity (the wrapper then takes the hash-table builders) and the hash-table builder names the limit.  The hash-table call
+    carries null pointers and relies on the check coming before any launch, so it is made on the emulator only."""
+    L = _lib.lib()
+    assert L.st_brick_pyramid_workspace_bytes(1, 1, 8, 1, (ctypes.c_int64 * 2)(1 << 28, 1)) == 0
+    assert L.st_brick_pyramid_workspace_bytes(1, 1, 8, 1, (ctypes.c_int64 * 2)((1 << 28) - 1, 1)) > 0
+    if backend.type == "cpu":
+        order = torch.zeros(1, dtype=torch.int32)
+        rc = L.st_build_strided_rulebook_seg(None, 1 << 28, None, None, 0, None, 0, None, None, 0, (ctypes.c_int32 * 3)(), None, None,
+                                             _lib.ptr(order), None, None, None)
+        assert rc != 0 and b"2^28" in L.st_last_error()
 
 
 def test_brick_path_leaves_the_network_outputs_unchanged(backend):

@@ -33,7 +33,8 @@ extern "C" {
  * 107: st_synth_points_seg and st_synth_philox added (no existing signature changed).
  * 108: st_prediction_metrics and its three size queries added (no existing signature changed).
  * 109: the st_render_* calls added (no existing signature changed).
- * 110: st_bridge_components_seg and its size query added (no existing signature changed). */
+ * 110: st_bridge_components_seg and its size query added (no existing signature changed).
+ * 111: st_segment_points_seg and its size query added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -540,6 +541,32 @@ int st_bridge_components_seg(const float* pts, int64_t n, const int32_t* vert_or
                              const int32_t* comp_off, int64_t n_comp, const int32_t* vert_seg_off, int nseg, float max_gap,
                              int64_t* edges, float* weights, int64_t cap, int64_t* n_bridges_host, int64_t* stats_host, void* ws,
                              int64_t ws_bytes, void* stream);
+
+/* ---- segmentation: every point to the tube of its cloud's skeleton it belongs to (csrc/segment.hip) --------------------
+ * replaces: util/queries.py:139-166 (skeleton_to_points) where a caller wants to know WHICH tube, tree and branch, not only how far.
+ *
+ * Tubes in `to_tubes()` order: a, b [m,3] end points, r1, r2 [m] end radii.  Per pair, float32 in k_nearest_tube's operation order:
+ * ab = b - a; dot = (x*x' + y*y') + z*z'; t = clip01(dot(ap, ab) / dot(ab, ab)); q = a + t*ab; r = (1 - t)*r1 + t*r2; v = q - p;
+ * residual = sqrtf(dot(v, v)) - r (negative inside the tube); score = |residual|.  A zero-length tube is the point a (t = 0); a tube
+ * with a non-finite end point or radius never wins, nor does a NaN score; a point with a non-finite coordinate gets no tube.
+ * Winner: the minimum of (bits of score, tube index).  max_distance >= 0: a best score > max_distance leaves the point unassigned
+ * (max_distance < 0: unbounded).  Unassigned: tube -1, residual +inf, vec 0, rad NaN.
+ * Point i of cloud s (pt_seg_off [nseg + 1]) sees the tubes [tube_seg_off[s], tube_seg_off[s + 1]); NULL offsets with nseg = 1: one
+ * cloud.  tube [n] is the position in the batched tube array.  m = 0 or a cloud without tubes: its points are unassigned.
+ * Every per-point output may be NULL.  tally (optional, [3*m] int64, zeroed by the call), per tube: points won, sum of
+ * llrintf(score * 2^24), sum of llrintf(residual * 2^24) (the scaled value clamped to +-2^62): integer sums, bit-identical
+ * from run to run and between the forms.
+ * form: 1 dense (every point against every tube of its cloud), 2 grid (the tubes binned into a per-cloud grid, a point walks the
+ * shells of cells around it until a float32-safe lower bound ends the search), 0 auto (by m / nseg).  The forms give identical bits.
+ * Enqueue-only.  Refused, nothing launched: n or m outside [0, 2^31), nseg outside [1, st_abi_entries(2)], nseg > 1 without both
+ * offset arrays, a NaN max_distance, a form outside 0..2 (-1); a workspace below st_segment_workspace_bytes(n, m, nseg) (-2; the
+ * size query returns -1 for sizes the call refuses).  After a grid call the first four int64 of the workspace hold: points that
+ * walked the grid, the sum and the maximum of the shells they visited, points that ended in a plain sweep. */
+int64_t st_segment_workspace_bytes(int64_t n, int64_t m, int nseg);
+int st_segment_points_seg(const float* pts, int64_t n, const int32_t* pt_seg_off, const float* a, const float* b, const float* r1,
+                          const float* r2, int64_t m, const int32_t* tube_seg_off, int nseg, float max_distance, int form,
+                          int32_t* tube, float* residual, float* vec, float* rad, int64_t* tally, void* ws, int64_t ws_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }

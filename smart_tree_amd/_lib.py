@@ -131,6 +131,8 @@ SIGNATURES = {
                                          ctypes.POINTER(I64), P, I64, P]),
     "st_skeleton_components": (c_int, [c_int, P, P, I64, P, P, P, P, P, P, c_float, c_int, c_int, P, P, P, P, P, P, P, P,
                                        P, P, ctypes.POINTER(I64), P, I64, P]),
+    "st_segment_workspace_bytes": (I64, [I64, I64, c_int]),
+    "st_segment_points_seg": (c_int, [P, I64, P, P, P, P, P, I64, P, c_int, c_float, c_int, P, P, P, P, P, P, I64, P]),
 }
 
 
@@ -156,7 +158,7 @@ ENQUEUE_ONLY = frozenset({
     "st_synth_points_seg", "st_synth_philox",
     "st_prediction_metrics_tally_ints", "st_prediction_metrics_tally_sums", "st_prediction_metrics_workspace_bytes", "st_prediction_metrics",
     "st_render_workspace_bytes", "st_render_clear", "st_render_points", "st_render_segments", "st_render_resolve",
-    "st_bridge_components_workspace_bytes",
+    "st_bridge_components_workspace_bytes", "st_segment_workspace_bytes", "st_segment_points_seg",
 })
 
 

@@ -56,6 +56,25 @@ def skeleton_tubes(skeleton):
     return t(xyz[start]), t(xyz[start + 1]), t(radii[start]), t(radii[start + 1])
 
 
+def skeleton_owners(skeleton) -> np.ndarray:
+    """int64 [B,4]: (tree, branch id, parent id, number of tubes) of every branch, in `skeleton_tubes` order -- the tubes of a
+    branch are contiguous, so the rows say who owns each tube.  `tree` is the tree's index in a `DisjointTreeSkeleton`, 0 for a
+    `TreeSkeleton`, the file's tree column for flat arrays; a branch of fewer than two points has no tube."""
+    if isinstance(skeleton, TreeSkeleton):
+        rows = [(0, k, br.parent_id, max(len(br) - 1, 0)) for k, br in skeleton.branches.items()]
+    elif isinstance(skeleton, DisjointTreeSkeleton):
+        rows = [(t, k, br.parent_id, max(len(br) - 1, 0)) for t, s in enumerate(skeleton.skeletons) for k, br in s.branches.items()]
+    else:
+        flat = np.asarray(skeleton["branches"], dtype=np.int64).reshape(-1, 5)
+        rows = [(int(r[0]), int(r[1]), int(r[2]), max(int(r[4]) - 1, 0)) for r in flat]
+    return np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+
+
+def branch_key(tree, branch):
+    """The id a branch is coloured by (`render.skeleton_items`, `CloudSegmentation.to_cloud`): 31 bits of tree * 65537 + branch."""
+    return (tree * 65537 + branch) & 0x7FFFFFFF
+
+
 def match(pts, rad, a, b, r1, r2, thresholds, ref_mode: int, per_sample: bool = True):
     """`st_skeleton_match` on device tensors: samples (pts [n,3], rad [n]) against tubes (a, b [m,3]; r1, r2 [m]).
     Returns {"hits": int64 [T], "sums": float64 [4]} (device, one buffer) and, with `per_sample`, "dist" [n], "idx" [n] int32,

@@ -5,7 +5,9 @@ match the reference.  Additive change: `process_cloud` returns the `DisjointTree
 reference only views / saves it).  An interactive window needs open3d and is out of scope: with a view flag
 set and `view_path` given, the views are rendered offscreen (smart_tree_amd/render.py) and written there as
 `model_output.png` / `skeleton.png`; without `view_path` a view flag raises.  `save_outputs` writes
-dependency-free files (util/file.py).
+dependency-free files (util/file.py).  Additive: `segment_cloud=True` assigns every point of the preprocessed cloud to
+a tree and a branch of the post-processed skeleton (segmentation.py) and keeps the result in `last_segmentation`;
+`save_outputs` then also writes `segmentation.npz` / `seg_cld.ply`, `view_skeletons` also `segmentation.png`.
 """
 from __future__ import annotations
 
@@ -25,7 +27,8 @@ class Pipeline:
     def __init__(self, preprocessing, model_inference, skeletonizer, repair_skeletons=False, smooth_skeletons=False,
                  smooth_kernel_size=0, prune_skeletons=False, min_skeleton_radius=0.0, min_skeleton_length=1000,
                  view_model_output=False, view_skeletons=False, save_outputs=False, save_path="/", branch_classes=[0],
-                 cmap=[[1, 0, 0], [0, 1, 0]], device=torch.device("cuda:0"), view_path=None):
+                 cmap=[[1, 0, 0], [0, 1, 0]], device=torch.device("cuda:0"), view_path=None, segment_cloud=False,
+                 segment_max_distance=None):
         self.preprocessing = preprocessing
         self.model_inference = model_inference
         self.skeletonizer = skeletonizer
@@ -44,6 +47,10 @@ class Pipeline:
         self.device = torch.device(device)
         self.view_path = view_path
         self.last_labelled_cloud = None
+        self.segment_cloud = segment_cloud
+        self.segment_max_distance = segment_max_distance
+        self.last_segmentation = None
+        self._segmented = None  # (cloud, its segmentation) the next write_views call draws
 
     def process_cloud(self, path: Path = None, cloud: Cloud = None) -> DisjointTreeSkeleton:
         cloud = load_cloud(path) if path is not None else cloud
@@ -58,6 +65,9 @@ class Pipeline:
         with profiling.stage("post_process"):
             self.post_process(skeleton)
             skeleton.skeletons  # materialise: device post-processing kernel, one D->H copy, BranchSkeleton objects
+        if self.segment_cloud:
+            self._segment(cloud, skeleton)
+            self._segmented = (cloud, self.last_segmentation)
         if self.view_model_output or self.view_skeletons:
             if self.view_path is None:
                 raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")
@@ -72,7 +82,17 @@ class Pipeline:
             verts, tris = skeleton_mesh(skeleton)  # reference pipeline.py:90: mesh.ply = the skeleton's tube mesh
             write_ply_mesh(sp / "mesh.ply", verts, tris)
             write_ply_points(sp / "cloud.ply", lc.xyz.cpu().numpy(), lc.rgb.cpu().numpy() if lc.rgb is not None else None)
+            if self.segment_cloud:  # the reference's fourth file name (pipeline.py:93 `seg_cld.ply`), here the points by branch
+                from .segmentation import save_segmentation
+                save_segmentation(sp, cloud, self.last_segmentation)
         return skeleton
+
+    def _segment(self, cloud: Cloud, skeleton) -> None:
+        """Every point the caller gave, in the skeleton's frame (the cloud `preprocessing` returned), to its tree and branch."""
+        from .segmentation import segment_cloud
+
+        with profiling.stage("segment_cloud"):
+            self.last_segmentation = segment_cloud(cloud, skeleton, max_distance=self.segment_max_distance, device=self.device)
 
     def process_clouds(self, clouds) -> list:
         """B independent clouds through ONE set of kernel launches (additive; the reference's unit of work is a batch
@@ -98,10 +118,14 @@ class Pipeline:
             parts = skeleton.split()  # device post-processing of all clouds, ONE device-to-host copy, per-cloud views
         if len(parts) != len(clouds):
             raise RuntimeError(f"process_clouds: {len(parts)} skeleton(s) for a batch of {len(clouds)} clouds")
+        if self.segment_cloud:  # each cloud against its own trees, one call
+            self._segment(batch, parts)
         if self.view_model_output or self.view_skeletons:
             if self.view_path is None:
                 raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")
+            drawn = list(zip(batch.split(), self.last_segmentation.split())) if self.segment_cloud else [None] * len(parts)
             for k, (cloud_k, part) in enumerate(zip(lc.split(), parts)):
+                self._segmented = drawn[k]
                 self.write_views(Path(self.view_path), cloud_k, part, prefix=f"cloud_{k}_")
         return parts
 
@@ -117,6 +141,11 @@ class Pipeline:
         if self.view_skeletons:
             items = cloud_items(labelled_cloud, "rgb") + skeleton_items(skeleton, device=self.device)
             write_png(path / f"{prefix}skeleton.png", look(items))
+            if self._segmented is not None:  # segment_cloud: the points by branch over the tubes in the same colours
+                cloud, seg = self._segmented
+                items = cloud_items(seg.to_cloud(cloud), "branch") + skeleton_items(skeleton, device=self.device)
+                write_png(path / f"{prefix}segmentation.png", look(items))
+        self._segmented = None
 
     def post_process(self, skeleton: DisjointTreeSkeleton) -> None:
         if self.prune_skeletons:

@@ -237,18 +237,11 @@ def medial_vector_items(cloud, colour=(0.0, 0.0, 0.0)):
 def skeleton_items(skeleton, device=None):
     """The tubes of a `TreeSkeleton`, a `DisjointTreeSkeleton` or the flat arrays of `save_skeleton_npz` (in `skeleton_tubes`
     order), coloured by branch."""
-    from .data_types.tree import DisjointTreeSkeleton, TreeSkeleton
-    from .evaluation import skeleton_tubes
+    from .evaluation import branch_key, skeleton_owners, skeleton_tubes
 
     a, b, r1, r2 = skeleton_tubes(skeleton)
-    if isinstance(skeleton, TreeSkeleton):
-        owner = [(0, k, len(br)) for k, br in skeleton.branches.items()]
-    elif isinstance(skeleton, DisjointTreeSkeleton):
-        owner = [(t, k, len(br)) for t, s in enumerate(skeleton.skeletons) for k, br in s.branches.items()]
-    else:
-        rows = np.asarray(skeleton["branches"], dtype=np.int64).reshape(-1, 5)
-        owner = [(int(r[0]), int(r[1]), int(r[4])) for r in rows]
-    ids = np.concatenate([np.full(max(n - 1, 0), (t * 65537 + k) & 0x7FFFFFFF, dtype=np.int32) for t, k, n in owner] or [np.zeros(0, np.int32)])
+    owner = skeleton_owners(skeleton)
+    ids = np.repeat(branch_key(owner[:, 0], owner[:, 1]), owner[:, 3]).astype(np.int32)
     if ids.shape[0] != a.shape[0]:
         raise RuntimeError(f"skeleton_items: {a.shape[0]} tubes for {ids.shape[0]} branch labels")
     dev = torch.device(device) if device is not None else torch.device("cuda:0")

@@ -9,14 +9,14 @@
 //   TreeSkeleton.smooth              tree.py:123-134 (zero-padded box filter, only when len > kernel)
 // Branches are visited in the order of the branch hierarchy (a parent always has a smaller id than its
 // children, so a child sees its parent already repaired, exactly like the reference's dict walk).
-// Float32 operation order is fixed and mirrored by oracle/pipeline_oracle.py:
-//   dot(a,b) = (ax*bx + ay*by) + az*bz, no contraction; length = sequential sum of segment norms;
-//   box filter = sequential sum of r*w with w = fl32(1/k).
+// Float32 operation order is fixed and mirrored by oracle/pipeline_oracle.py: the repair's point-to-tube pair and the dot product
+//   are st_tube.h's; length = sequential sum of segment norms; box filter = sequential sum of r*w with w = fl32(1/k).
 //
 // Geometry layout: branch b owns slots [start[b], start[b] + len[b] + 1); slot start[b] is reserved for
 // the connection point `repair` prepends (its radius slot must already hold a copy of the first
 // radius, tree.py:92), the extracted path sits in start[b]+1 ...
 #include "st_common.h"
+#include "st_tube.h"
 
 #define PP_BLOCK 1024  // 16 wavefronts: the per-branch work is a chain of dependent loads, more waves = more branches in flight
 #define PP_WAVES (PP_BLOCK / 64)
@@ -45,28 +45,23 @@ __device__ __forceinline__ float pp_ldf(const float* p) {
     return __uint_as_float(__hip_atomic_load((const unsigned*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-__device__ __forceinline__ float pp_dot(const float* a, const float* b) {
-    float s = a[0] * b[0];
-    float t = a[1] * b[1];
-    s = s + t;
-    t = a[2] * b[2];
-    return s + t;
-}
-
 // Score of one tube (a, b, radii ra, rb) for the connection point of a branch whose first vertex is pt: |distance to the
 // segment - interpolated radius| (pts_to_nearest_tube_gpu, util/queries.py:107-133), as the ordered bit pattern the argmin
-// works on (NaN counts as minimal).  t comes back for the caller that has to place the projection.
-__device__ __forceinline__ unsigned pp_tube_bits(const float* a, const float* bb, float ra, float rb, const float* pt, float* t_out) {
-    const float ab[3] = {bb[0] - a[0], bb[1] - a[1], bb[2] - a[2]};
-    const float ap[3] = {pt[0] - a[0], pt[1] - a[1], pt[2] - a[2]};
-    float t = pp_dot(ap, ab) / pp_dot(ab, ab);
-    t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-    const float proj[3] = {a[0] + t * ab[0], a[1] + t * ab[1], a[2] + t * ab[2]};
-    const float r = (1.0f - t) * ra + t * rb;
-    const float d[3] = {proj[0] - pt[0], proj[1] - pt[1], proj[2] - pt[2]};
-    const float score = fabsf(sqrtf(pp_dot(d, d)) - r);
-    *t_out = t;
-    return score != score ? 0u : __float_as_uint(score) + 1u;  // >= 0: bits are ordered
+// works on (NaN counts as minimal).
+__device__ __forceinline__ unsigned pp_tube_bits(const float* a, const float* bb, float ra, float rb, const float* pt) {
+    float4 A, B;
+    float ab2;
+    st_tube_record(a, bb, &ra, &rb, 0, &A, &B, &ab2, 0);
+    return st_score_key(fabsf(st_tube_pair(pt[0], pt[1], pt[2], A, B, ab2).res));
+}
+// The connection point of that branch on the tube (a, b): the tip + the vector to its projection (tree.py:89).
+__device__ __forceinline__ void pp_connect(const float* a, const float* bb, const float* pt, float* out) {
+    float4 A, B;
+    float ab2;
+    const float r = 0.0f;
+    st_tube_record(a, bb, &r, &r, 0, &A, &B, &ab2, 0);
+    const StPair<float> c = st_tube_project(st_tube_t_div(pt[0], pt[1], pt[2], A, B, ab2), pt[0], pt[1], pt[2], A, B);
+    out[0] = pt[0] + c.vx; out[1] = pt[1] + c.vy; out[2] = pt[2] + c.vz;
 }
 // (score, tube index) as one key whose MAXIMUM is the minimum score at the smallest index
 __device__ __forceinline__ unsigned long long pp_key(unsigned bits, unsigned i) {
@@ -109,7 +104,7 @@ __global__ void __launch_bounds__(PP_WIDE_BLOCK) k_pp_branch(PpArgs A) {
                 if (i + 1 < n) {
                     const float d[3] = {A.xyz[3 * (s + i + 1)] - A.xyz[3 * (s + i)], A.xyz[3 * (s + i + 1) + 1] - A.xyz[3 * (s + i) + 1],
                                         A.xyz[3 * (s + i + 1) + 2] - A.xyz[3 * (s + i) + 2]};
-                    seg = sqrtf(pp_dot(d, d));
+                    seg = sqrtf(st_dot3(d[0], d[1], d[2], d[0], d[1], d[2]));
                 }
                 const int cnt = (n - 1 - i0) < 64 ? (n - 1 - i0) : 64;
                 for (int j = 0; j < cnt; j++)  // j is wave-uniform: v_readlane, not a cross-lane permute through LDS
@@ -131,12 +126,12 @@ __global__ void __launch_bounds__(PP_WIDE_BLOCK) k_pp_branch(PpArgs A) {
                 const int ps = A.start[b0 + p] + 1, pn = A.len[b0 + p], s = A.start[g];
                 const float pt[3] = {A.xyz[3 * (s + 1)], A.xyz[3 * (s + 1) + 1], A.xyz[3 * (s + 1) + 2]};
                 for (int j = lane; j + 1 < pn; j += 64) {
-                    float a[3], bb[3], t;
+                    float a[3], bb[3];
                     for (int k = 0; k < 3; k++) {
                         a[k] = A.xyz[3 * (ps + j) + k];
                         bb[k] = A.xyz[3 * (ps + j + 1) + k];
                     }
-                    const unsigned long long k2 = pp_key(pp_tube_bits(a, bb, A.rad_in[ps + j], A.rad_in[ps + j + 1], pt, &t), (unsigned)j);
+                    const unsigned long long k2 = pp_key(pp_tube_bits(a, bb, A.rad_in[ps + j], A.rad_in[ps + j + 1], pt), (unsigned)j);
                     key = k2 > key ? k2 : key;
                 }
                 for (int d = 32; d > 0; d >>= 1) {  // wave max of the inverted key = minimum score, smallest index
@@ -275,23 +270,16 @@ __global__ void __launch_bounds__(PP_BLOCK) k_pp_tree(PpArgs A) {
         for (int level = 1; level <= maxdepth; level++) {
             if (lev == level) {
                 unsigned long long key = key_imm;
-                float a[3] = {ai[0], ai[1], ai[2]}, bb[3] = {bi[0], bi[1], bi[2]}, t;
+                float a[3] = {ai[0], ai[1], ai[2]}, bb[3] = {bi[0], bi[1], bi[2]};
                 if (prep) {
                     float a0[3];
                     for (int k = 0; k < 3; k++) a0[k] = pp_ldf(&A.xyz[3 * ps + k]);  // written one level earlier by another lane: through L2
-                    const unsigned long long k0 = pp_key(pp_tube_bits(a0, b0v, ra0, rb0, pt, &t), 0u);
+                    const unsigned long long k0 = pp_key(pp_tube_bits(a0, b0v, ra0, rb0, pt), 0u);
                     if (k0 > key) {
                         for (int k = 0; k < 3; k++) { a[k] = a0[k]; bb[k] = b0v[k]; }
                     }
                 }
-                const float ab[3] = {bb[0] - a[0], bb[1] - a[1], bb[2] - a[2]};
-                const float ap[3] = {pt[0] - a[0], pt[1] - a[1], pt[2] - a[2]};
-                t = pp_dot(ap, ab) / pp_dot(ab, ab);
-                t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-                for (int k = 0; k < 3; k++) {
-                    const float proj = a[k] + t * ab[k];
-                    A.xyz[3 * s + k] = pt[k] + (proj - pt[k]);  // tree.py:89: tip + vector to the projection
-                }
+                pp_connect(a, bb, pt, &A.xyz[3 * s]);
                 A.repaired[b0 + b] = 1;
             }
             __threadfence();
@@ -311,7 +299,6 @@ __global__ void __launch_bounds__(PP_BLOCK) k_pp_tree(PpArgs A) {
             // extracted path (its tube j is tube j + 1 of a repaired parent), and the tube from the parent's connection point
             const unsigned* slot = (const unsigned*)(A.rad_out + s);
             unsigned long long key = ((unsigned long long)slot[0] << 32) | slot[1];
-            float t;
             if (prep) {
                 if (key) key -= 1;  // index j -> j + 1 (the low word holds 0xffffffff - j)
                 float a[3], bb[3];
@@ -319,7 +306,7 @@ __global__ void __launch_bounds__(PP_BLOCK) k_pp_tree(PpArgs A) {
                     a[k] = pp_ldf(&A.xyz[3 * ps + k]);  // written one level earlier by another lane: through L2
                     bb[k] = A.xyz[3 * (ps + 1) + k];
                 }
-                const unsigned long long k0 = pp_key(pp_tube_bits(a, bb, A.rad_in[ps], A.rad_in[ps + 1], pt, &t), 0u);
+                const unsigned long long k0 = pp_key(pp_tube_bits(a, bb, A.rad_in[ps], A.rad_in[ps + 1], pt), 0u);
                 key = k0 > key ? k0 : key;
             }
             const int i = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
@@ -328,14 +315,7 @@ __global__ void __launch_bounds__(PP_BLOCK) k_pp_tree(PpArgs A) {
                 a[k] = (prep && i == 0) ? pp_ldf(&A.xyz[3 * ps + k]) : A.xyz[3 * (ps + i) + k];
                 bb[k] = A.xyz[3 * (ps + i + 1) + k];
             }
-            const float ab[3] = {bb[0] - a[0], bb[1] - a[1], bb[2] - a[2]};
-            const float ap[3] = {pt[0] - a[0], pt[1] - a[1], pt[2] - a[2]};
-            t = pp_dot(ap, ab) / pp_dot(ab, ab);
-            t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-            for (int k = 0; k < 3; k++) {
-                const float proj = a[k] + t * ab[k];
-                A.xyz[3 * s + k] = pt[k] + (proj - pt[k]);  // tree.py:89: tip + vector to the projection
-            }
+            pp_connect(a, bb, pt, &A.xyz[3 * s]);
             A.repaired[b0 + b] = 1;
         }
         __threadfence();

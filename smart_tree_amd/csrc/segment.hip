@@ -1,20 +1,18 @@
 // st_segment_points_seg: which tube of its cloud's skeleton every point belongs to, batched, with per-tube statistics.
 //
 // The reference has `skeleton_to_points` (util/queries.py:139-166), a dense sweep that returns distances only; nothing in it says
-// which tree and which branch a point belongs to.  st_points_to_nearest_tube (queries.hip) is that sweep; this file keeps its
-// pair expression and adds what a segmentation needs: a per-cloud tube range, an "unassigned" outcome, a strict total order of
-// the candidates, per-tube tallies -- and a grid over the TUBES so that a point only meets the tubes around it.
+// which tree and which branch a point belongs to.  This file scores the same pairs and adds what a segmentation needs: a per-cloud
+// tube range, an "unassigned" outcome, a strict total order of the candidates, per-tube tallies -- and a grid over the TUBES so
+// that a point only meets the tubes around it.
 //
-// Pair (float32, this operation order, no contraction -- k_nearest_tube's, mirrored afresh by tests/segment_oracle.py):
-//   ab = b - a;  dot(u, v) = (ux*vx + uy*vy) + uz*vz;  t = clip01(dot(p - a, ab) / dot(ab, ab));  q = a + t*ab
-//   r = (1 - t)*r1 + t*r2;  v = q - p;  residual = sqrtf(dot(v, v)) - r (negative inside the tube);  score = |residual|
-// Deviations from k_nearest_tube, on purpose: a zero-length tube (dot(ab, ab) == 0) is the point a with t = 0; a tube with a
+// Pair: st_tube.h's (residual = distance to the axis - radius, score = |residual|; tests/segment_oracle.py restates it afresh).
+// This file's own rules, on purpose: a zero-length tube (dot(ab, ab) == 0) is the point a with t = 0; a tube with a
 // non-finite end point or radius never wins; a point with a non-finite coordinate gets no tube; a NaN score (overflow) never wins.
 // Winner: the minimum of (bits of score, tube index).  max_distance >= 0: a best score > max_distance leaves the point unassigned
 // (tube -1, residual +inf, vec 0, rad NaN).  tally[3*t ..]: points won, sum of llrintf(score * 2^24), sum of llrintf(residual * 2^24)
 // (the scaled value clamped to +-2^62): integer sums, the same in every run and every form.
 //
-// Form 1, dense: k_nearest_tube's loop -- two points per lane, the tubes staged through LDS in tiles -- over the union of the tube
+// Form 1, dense: two points per lane (the packed pair), the tubes staged through LDS in tiles, over the union of the tube
 //   ranges of the clouds a workgroup's points belong to; a lane takes a tube only inside its own cloud's range.  The loop keeps
 //   (score bits, index) only; the winner's pair is evaluated once more at the end (the same operations, the same bits).
 // Form 2, grid: per cloud a uniform grid over the boxes of the tubes' axes, each inflated by max(r1, r2, 0); a tube is entered
@@ -38,6 +36,7 @@
 // points that walked shells, the sum and the maximum of their shell counts, points that ended in the sweep (tools/bench_segment.py).
 #include "st_common.h"
 #include "st_grid.h"
+#include "st_tube.h"
 
 #define SG_BLOCK 256
 #define SG_TILE 512
@@ -46,7 +45,6 @@
 #define SG_MAX_SHELL 4
 #define SG_AUTO_GRID_M 20480  // dense and grid cost the same near 19 400 tubes per cloud (profiles/segment_bench.json)
 #define SG_PLAN_ROUNDS 96
-typedef float sg_f2 __attribute__((ext_vector_type(2)));  // two points per lane: v_pk_{add,mul}_f32 do both at once
 
 struct SgCloud {
     float lo[3];
@@ -63,46 +61,21 @@ struct SgStats {
     unsigned long long walked, shells, max_shells, swept;
 };
 
-__device__ __forceinline__ float sg_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    float s = ax * bx;
-    float t = ay * by;
-    s = s + t;
-    t = az * bz;
-    return s + t;
-}
-__device__ __forceinline__ sg_f2 sg_dot2(sg_f2 ax, sg_f2 ay, sg_f2 az, sg_f2 bx, sg_f2 by, sg_f2 bz) {
-    sg_f2 s = ax * bx;
-    sg_f2 t = ay * by;
-    s = s + t;
-    t = az * bz;
-    return s + t;
-}
-__device__ __forceinline__ float sg_clip01(float t) { return t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t); }  // NaN stays NaN
-__device__ __forceinline__ bool sg_finite(float v) { return fabsf(v) <= 3.4028234e38f; }
-
-struct SgPair {
-    float vx, vy, vz, r, res;
-};
-// the pair expression; (dx, dy, dz) = b - a and ab2 = dot(ab, ab) formed by the caller (once per tube)
-__device__ __forceinline__ SgPair sg_pair(float px, float py, float pz, float ax, float ay, float az, float dx, float dy, float dz,
-                                          float ab2, float r1, float r2) {
-    const float num = sg_dot(px - ax, py - ay, pz - az, dx, dy, dz);
-    const float t = ab2 == 0.0f ? 0.0f : sg_clip01(num / ab2);
-    float qx = t * dx, qy = t * dy, qz = t * dz;
-    qx = ax + qx; qy = ay + qy; qz = az + qz;
-    float r = (1.0f - t) * r1;
-    const float r_hi = t * r2;
-    r = r + r_hi;
-    SgPair o;
-    o.vx = qx - px; o.vy = qy - py; o.vz = qz - pz;
-    o.r = r;
-    o.res = sqrtf(sg_dot(o.vx, o.vy, o.vz, o.vx, o.vy, o.vz)) - r;
-    return o;
-}
-
 __device__ __forceinline__ bool sg_tube_ok(const float* a, const float* b, const float* r1, const float* r2, int64_t g) {
-    return sg_finite(a[3 * g]) && sg_finite(a[3 * g + 1]) && sg_finite(a[3 * g + 2]) && sg_finite(b[3 * g]) && sg_finite(b[3 * g + 1]) &&
-           sg_finite(b[3 * g + 2]) && sg_finite(r1[g]) && sg_finite(r2[g]);
+    return st_finite(a[3 * g]) && st_finite(a[3 * g + 1]) && st_finite(a[3 * g + 2]) && st_finite(b[3 * g]) && st_finite(b[3 * g + 1]) &&
+           st_finite(b[3 * g + 2]) && st_finite(r1[g]) && st_finite(r2[g]);
+}
+
+// The tube record as every loop here reads it.  A tube with a non-finite value: its radius becomes NaN, and with it every score.
+// A zero-length tube (t = 0) without a select in the pair loops: with ab = 0 and the divisor 1 the quotient is +-0, q is a and r is
+// r1 -- the score's bits are those of t = 0 (a zero's sign never reaches them; the outputs are formed by sg_finish, which takes
+// t = 0 literally).
+__device__ __forceinline__ void sg_tube_record(const float* a, const float* b, const float* r1, const float* r2, int64_t g, float4* ta,
+                                               float4* tb, float* tab2, int64_t j) {
+    const bool ok = sg_tube_ok(a, b, r1, r2, g);
+    st_tube_record(a, b, r1, r2, g, ta, tb, tab2, j);
+    if (!ok) ta[j].w = __uint_as_float(0x7fc00000u);
+    if (tab2[j] == 0.0f) { tb[j].x = 0.0f; tb[j].y = 0.0f; tb[j].z = 0.0f; tab2[j] = 1.0f; }
 }
 
 __device__ __forceinline__ long long sg_fix(float v) {  // llrintf(v * 2^24), the scaled value clamped to +-2^62
@@ -115,12 +88,14 @@ __device__ __forceinline__ long long sg_fix(float v) {  // llrintf(v * 2^24), th
 __device__ __forceinline__ int sg_finish(int64_t i, float px, float py, float pz, int best, float max_distance, const float* a,
                                          const float* b, const float* r1, const float* r2, int32_t* tube, float* residual, float* vec,
                                          float* rad, float* res_out) {
-    SgPair w = {0.0f, 0.0f, 0.0f, __uint_as_float(0x7fc00000u), __uint_as_float(0x7f800000u)};
+    StPair<float> w;
+    w.vx = 0.0f; w.vy = 0.0f; w.vz = 0.0f; w.r = __uint_as_float(0x7fc00000u); w.res = __uint_as_float(0x7f800000u);
     if (best >= 0) {
-        const int64_t g = best;
-        const float ax = a[3 * g], ay = a[3 * g + 1], az = a[3 * g + 2];
-        const float dx = b[3 * g] - ax, dy = b[3 * g + 1] - ay, dz = b[3 * g + 2] - az;
-        const SgPair c = sg_pair(px, py, pz, ax, ay, az, dx, dy, dz, sg_dot(dx, dy, dz, dx, dy, dz), r1[g], r2[g]);
+        float4 A, B;
+        float ab2;
+        st_tube_record(a, b, r1, r2, best, &A, &B, &ab2, 0);
+        const float t = ab2 == 0.0f ? 0.0f : st_tube_t_div(px, py, pz, A, B, ab2);
+        const StPair<float> c = st_tube_pair_at(t, px, py, pz, A, B);
         if (max_distance >= 0.0f && fabsf(c.res) > max_distance) best = -1;
         else w = c;
     }
@@ -195,56 +170,27 @@ __global__ void __launch_bounds__(SG_BLOCK) k_sg_dense(const float* __restrict__
         lo0 = tube_seg_off[s0]; cnt0 = (unsigned)(tube_seg_off[s0 + 1] - lo0);
         lo1 = tube_seg_off[s1]; cnt1 = (unsigned)(tube_seg_off[s1 + 1] - lo1);
     }
-    const sg_f2 px = {live0 ? pts[3 * i0] : 0.0f, live1 ? pts[3 * i1] : 0.0f};
-    const sg_f2 py = {live0 ? pts[3 * i0 + 1] : 0.0f, live1 ? pts[3 * i1 + 1] : 0.0f};
-    const sg_f2 pz = {live0 ? pts[3 * i0 + 2] : 0.0f, live1 ? pts[3 * i1 + 2] : 0.0f};
+    const st_f2 px = {live0 ? pts[3 * i0] : 0.0f, live1 ? pts[3 * i1] : 0.0f};
+    const st_f2 py = {live0 ? pts[3 * i0 + 1] : 0.0f, live1 ? pts[3 * i1 + 1] : 0.0f};
+    const st_f2 pz = {live0 ? pts[3 * i0 + 2] : 0.0f, live1 ? pts[3 * i1 + 2] : 0.0f};
     unsigned key0 = SG_NONE, key1 = SG_NONE;
     int best0 = -1, best1 = -1;
-    for (int64_t base = t_begin; base < t_end; base += SG_TILE) {
-        const int cnt = (int)(t_end - base < SG_TILE ? t_end - base : SG_TILE);
-        __syncthreads();  // the previous tile is no longer read
-        for (int j = threadIdx.x; j < cnt; j += SG_BLOCK) {
-            const int64_t g = base + j;
-            const float ax = a[3 * g], ay = a[3 * g + 1], az = a[3 * g + 2];
-            float dx = b[3 * g] - ax, dy = b[3 * g + 1] - ay, dz = b[3 * g + 2] - az;
-            float ab2 = sg_dot(dx, dy, dz, dx, dy, dz);
-            // A zero-length tube (t = 0) without a select in the pair loop: with ab = 0 and the divisor 1 the quotient is +-0, q is a
-            // and r is r1 -- the score's bits are those of t = 0 (a zero's sign never reaches them; the outputs are formed by
-            // sg_finish, which takes t = 0 literally).
-            if (ab2 == 0.0f) { dx = 0.0f; dy = 0.0f; dz = 0.0f; ab2 = 1.0f; }
-            // a tube with a non-finite value: its radius becomes NaN, and with it every score
-            ta[j] = make_float4(ax, ay, az, sg_tube_ok(a, b, r1, r2, g) ? r1[g] : __uint_as_float(0x7fc00000u));
-            tb[j] = make_float4(dx, dy, dz, r2[g]);
-            tab2[j] = ab2;
-        }
-        __syncthreads();
-        if (!live0) continue;
-        for (int j = 0; j < cnt; j++) {
-            const float4 A = ta[j], B = tb[j];
-            const float ab2 = tab2[j];
-            const sg_f2 num = sg_dot2(px - A.x, py - A.y, pz - A.z, sg_f2{B.x, B.x}, sg_f2{B.y, B.y}, sg_f2{B.z, B.z});
-            const sg_f2 t = {sg_clip01(num.x / ab2), sg_clip01(num.y / ab2)};
-            sg_f2 qx = t * B.x, qy = t * B.y, qz = t * B.z;
-            qx = A.x + qx; qy = A.y + qy; qz = A.z + qz;
-            sg_f2 r = (1.0f - t) * A.w;
-            const sg_f2 r_hi = t * B.w;
-            r = r + r_hi;
-            const sg_f2 vx = qx - px, vy = qy - py, vz = qz - pz;
-            const sg_f2 d2 = sg_dot2(vx, vy, vz, vx, vy, vz);
-            const unsigned k0 = __float_as_uint(fabsf(sqrtf(d2.x) - r.x)), k1 = __float_as_uint(fabsf(sqrtf(d2.y) - r.y));
-            const int g = (int)(base + j);
+    st_tube_sweep<SG_BLOCK, SG_TILE>(
+        t_begin, t_end, live0, [&](int64_t g, int j) { sg_tube_record(a, b, r1, r2, g, ta, tb, tab2, j); },
+        [&](int j, int g) {
+            const StPair<st_f2> c = st_tube_pair(px, py, pz, ta[j], tb[j], tab2[j]);
+            const unsigned k0 = __float_as_uint(fabsf(c.res.x)), k1 = __float_as_uint(fabsf(c.res.y));
             if (k0 < key0 && (!BATCH || (unsigned)(g - lo0) < cnt0)) { key0 = k0; best0 = g; }  // score >= 0: the bits order like the values
             if (k1 < key1 && (!BATCH || (unsigned)(g - lo1) < cnt1)) { key1 = k1; best1 = g; }
-        }
-    }
+        });
     int won0 = -1, won1 = -1;
     float res0 = 0.0f, res1 = 0.0f;
     if (live0) {
-        if (!(sg_finite(px.x) && sg_finite(py.x) && sg_finite(pz.x))) best0 = -1;
+        if (!(st_finite(px.x) && st_finite(py.x) && st_finite(pz.x))) best0 = -1;
         won0 = sg_finish(i0, px.x, py.x, pz.x, best0, max_distance, a, b, r1, r2, tube, residual, vec, rad, &res0);
     }
     if (live1) {
-        if (!(sg_finite(px.y) && sg_finite(py.y) && sg_finite(pz.y))) best1 = -1;
+        if (!(st_finite(px.y) && st_finite(py.y) && st_finite(pz.y))) best1 = -1;
         won1 = sg_finish(i1, px.y, py.y, pz.y, best1, max_distance, a, b, r1, r2, tube, residual, vec, rad, &res1);
     }
     if (tally == nullptr) return;  // (the same in every lane)
@@ -406,22 +352,16 @@ __global__ void __launch_bounds__(SG_BLOCK) k_sg_bin(const float* a, const float
 // offer tube g to a point
 __device__ __forceinline__ void sg_offer(float px, float py, float pz, int g, const float4* ta, const float4* tb, const float* tab2,
                                          unsigned* key, int* best) {
-    const float4 A = ta[g], B = tb[g];
-    const SgPair c = sg_pair(px, py, pz, A.x, A.y, A.z, B.x, B.y, B.z, tab2[g], A.w, B.w);
-    const unsigned k = __float_as_uint(fabsf(c.res));
+    const unsigned k = __float_as_uint(fabsf(st_tube_pair(px, py, pz, ta[g], tb[g], tab2[g]).res));
     if (k < *key || (k == *key && g < *best)) { *key = k; *best = g; }
 }
 
-// the tubes as the pair reads them: (a, r1 -- NaN for a tube that never wins), (b - a, r2), dot(ab, ab)
+// the tubes as the pair reads them, for the grid form's gathers
 __global__ void __launch_bounds__(SG_BLOCK) k_sg_pack(const float* a, const float* b, const float* r1, const float* r2, int64_t m,
                                                       float4* ta, float4* tb, float* tab2) {
     const int64_t g = (int64_t)blockIdx.x * SG_BLOCK + threadIdx.x;
     if (g >= m) return;
-    const float ax = a[3 * g], ay = a[3 * g + 1], az = a[3 * g + 2];
-    const float dx = b[3 * g] - ax, dy = b[3 * g + 1] - ay, dz = b[3 * g + 2] - az;
-    ta[g] = make_float4(ax, ay, az, sg_tube_ok(a, b, r1, r2, g) ? r1[g] : __uint_as_float(0x7fc00000u));
-    tb[g] = make_float4(dx, dy, dz, r2[g]);
-    tab2[g] = sg_dot(dx, dy, dz, dx, dy, dz);
+    sg_tube_record(a, b, r1, r2, g, ta, tb, tab2, g);
 }
 
 __global__ void __launch_bounds__(SG_BLOCK) k_sg_query(const float* __restrict__ pts, int64_t n, const int32_t* __restrict__ pt_seg_off,
@@ -447,7 +387,7 @@ __global__ void __launch_bounds__(SG_BLOCK) k_sg_query(const float* __restrict__
         const float px = pts[3 * i], py = pts[3 * i + 1], pz = pts[3 * i + 2];
         unsigned key = SG_NONE;
         int best = -1;
-        if (sg_finite(px) && sg_finite(py) && sg_finite(pz)) {
+        if (st_finite(px) && st_finite(py) && st_finite(pz)) {
             bool sweep = c->sweep != 0;
             if (!sweep) {
                 const int dx = c->dim[0], dy = c->dim[1], dz = c->dim[2];

@@ -9,41 +9,21 @@
 // Sampling (the contract; it deviates from the reference on purpose, DESIGN.md "Evaluation"): v = b - a,
 //   len = sqrtf((vx*vx + vy*vy) + vz*vz), n = ceil((double)len / spacing), n = 0 for a zero or non-finite len;
 //   sample k of n: f = (float)k / (float)n, point a + v*f, radius r1 + (r2 - r1)*f.  Tube i owns [off[i], off[i] + n_i).
-// Matching, float32 with a fixed order (mirrored by tests/eval_oracle.py):
-//   dot(u,w) = (ux*wx + uy*wy) + uz*wz, no contraction;  inv = 1 / dot(ab,ab) (IEEE division, once per tube; 0 when
-//   dot(ab,ab) == 0, so a zero-length tube is the point a);  t = dot(ap,ab) * inv;  t = t > 0 ? t : 0 (a NaN becomes 0),
-//   t = t < 1 ? t : 1;  q = a + t*ab;  d2 = dot(q - p, q - p).  The winner is the first tube with the smallest d2; a NaN or
-//   infinite d2 never wins (idx = -1, dist = +inf, tube_rad = NaN when no tube gives a finite d2).
+// Matching (the pieces and their float32 order are st_tube.h's; tests/eval_oracle.py restates them afresh): per tube, once,
+//   inv = 1 / dot(ab,ab) (IEEE division; 0 when dot(ab,ab) == 0, so a zero-length tube is the point a); per pair the reciprocal
+//   form of t (a NaN becomes 0), the projection q and d2 = dot(q - p, q - p).  The winner is the first tube with the smallest d2; a
+//   NaN or infinite d2 never wins (idx = -1, dist = +inf, tube_rad = NaN when no tube gives a finite d2).
 // The pair loop keeps only (d2, t, index): ~30 float32 operations per two pairs on packed multiplies / adds, two LDS
 // broadcast reads per tube.  The square root and the radius are taken once per sample after the loop.  COMPUTE-bound.
 // Tally: hits with integer atomics (one add per threshold per workgroup), the float64 sums as one partial per workgroup in
 // the workspace, added in workgroup order by a second launch -- no float atomics, the tally is a function of the inputs alone.
 #include "st_common.h"
+#include "st_tube.h"
 
 #define SE_BLOCK 256
 #define SE_TILE 512
 #define SE_MAX_THR 32
 #define SE_SUMS 4
-typedef float se_f2 __attribute__((ext_vector_type(2)));  // two samples per lane: v_pk_{add,mul}_f32 do both at once
-
-__device__ __forceinline__ float se_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    float s = ax * bx;
-    float t = ay * by;
-    s = s + t;
-    t = az * bz;
-    return s + t;
-}
-__device__ __forceinline__ se_f2 se_dot2(se_f2 ax, se_f2 ay, se_f2 az, se_f2 bx, se_f2 by, se_f2 bz) {
-    se_f2 s = ax * bx;
-    se_f2 t = ay * by;
-    s = s + t;
-    t = az * bz;
-    return s + t;
-}
-__device__ __forceinline__ float se_clip01(float t) {  // NaN -> 0, -0 -> +0
-    t = t > 0.0f ? t : 0.0f;
-    return t < 1.0f ? t : 1.0f;
-}
 
 // ------------------------------------------------------------------------------------------------ sampling ---
 // Number of samples of one tube (saturated at 2^31: the host refuses such a total) and its axis vector.
@@ -51,7 +31,7 @@ __device__ __forceinline__ uint32_t se_tube_samples(const float* __restrict__ a,
                                                     float& ax, float& ay, float& az, float& vx, float& vy, float& vz) {
     ax = a[3 * i]; ay = a[3 * i + 1]; az = a[3 * i + 2];
     vx = b[3 * i] - ax; vy = b[3 * i + 1] - ay; vz = b[3 * i + 2] - az;
-    const float len = sqrtf(se_dot(vx, vy, vz, vx, vy, vz));
+    const float len = sqrtf(st_dot3(vx, vy, vz, vx, vy, vz));
     if (!(len > 0.0f) || !(len <= 3.402823466e+38f)) return 0u;  // zero, NaN or infinite
     const double c = ceil((double)len / spacing);
     return c >= 2147483648.0 ? 0x80000000u : (uint32_t)c;
@@ -159,52 +139,39 @@ __global__ void __launch_bounds__(SE_BLOCK) k_skeleton_match(const float* __rest
                                                              float* __restrict__ dist, int32_t* __restrict__ idx,
                                                              float* __restrict__ tube_rad, unsigned long long* __restrict__ hits,
                                                              double* __restrict__ partial) {
-    // per tube: (a.xyz, 1 / ab.ab), (ab.xyz, -) -- two LDS reads per tube, the same address in every lane (broadcast)
+    // per tube: (a.xyz, 1 / ab.ab), (ab.xyz, r2: not read) -- two LDS reads per tube, the same address in every lane (broadcast)
     __shared__ float4 ta[SE_TILE], tb[SE_TILE];
     __shared__ unsigned s_hits[SE_BLOCK / 64][SE_MAX_THR];
     __shared__ double s_sum[SE_BLOCK / 64][SE_SUMS];
     const int64_t i0 = ((int64_t)blockIdx.x * SE_BLOCK + threadIdx.x) * 2, i1 = i0 + 1;
     const bool live0 = i0 < n, live1 = i1 < n;
-    const se_f2 px = {live0 ? pts[3 * i0] : 0.0f, live1 ? pts[3 * i1] : 0.0f};
-    const se_f2 py = {live0 ? pts[3 * i0 + 1] : 0.0f, live1 ? pts[3 * i1 + 1] : 0.0f};
-    const se_f2 pz = {live0 ? pts[3 * i0 + 2] : 0.0f, live1 ? pts[3 * i1 + 2] : 0.0f};
+    const st_f2 px = {live0 ? pts[3 * i0] : 0.0f, live1 ? pts[3 * i1] : 0.0f};
+    const st_f2 py = {live0 ? pts[3 * i0 + 1] : 0.0f, live1 ? pts[3 * i1 + 1] : 0.0f};
+    const st_f2 pz = {live0 ? pts[3 * i0 + 2] : 0.0f, live1 ? pts[3 * i1 + 2] : 0.0f};
     const float inf = __uint_as_float(0x7f800000u);
     float bd0 = inf, bd1 = inf, bt0 = 0.0f, bt1 = 0.0f;
     int best0 = -1, best1 = -1;
-    for (int64_t base = 0; base < m; base += SE_TILE) {
-        const int cnt = (int)(m - base < SE_TILE ? m - base : SE_TILE);
-        __syncthreads();  // the previous tile is no longer read
-        for (int j = threadIdx.x; j < cnt; j += SE_BLOCK) {
-            const int64_t g = base + j;
-            const float ax = a[3 * g], ay = a[3 * g + 1], az = a[3 * g + 2];
-            const float dx = b[3 * g] - ax, dy = b[3 * g + 1] - ay, dz = b[3 * g + 2] - az;
-            const float ab2 = se_dot(dx, dy, dz, dx, dy, dz);
-            ta[j] = make_float4(ax, ay, az, ab2 == 0.0f ? 0.0f : 1.0f / ab2);
-            tb[j] = make_float4(dx, dy, dz, 0.0f);
-        }
-        __syncthreads();
-        if (!live0) continue;
-        for (int j = 0; j < cnt; j++) {
-            const float4 A = ta[j], B = tb[j];
-            const se_f2 bx = {B.x, B.x}, by = {B.y, B.y}, bz = {B.z, B.z};
-            se_f2 t = se_dot2(px - A.x, py - A.y, pz - A.z, bx, by, bz) * A.w;
-            t.x = se_clip01(t.x);
-            t.y = se_clip01(t.y);
-            se_f2 qx = t * bx, qy = t * by, qz = t * bz;
-            qx = A.x + qx; qy = A.y + qy; qz = A.z + qz;
-            const se_f2 vx = qx - px, vy = qy - py, vz = qz - pz;
-            const se_f2 d2 = se_dot2(vx, vy, vz, vx, vy, vz);
-            if (d2.x < bd0) { bd0 = d2.x; bt0 = t.x; best0 = (int)(base + j); }  // strict: first minimum; NaN / inf never win
-            if (d2.y < bd1) { bd1 = d2.y; bt1 = t.y; best1 = (int)(base + j); }
-        }
-    }
+    st_tube_sweep<SE_BLOCK, SE_TILE>(
+        0, m, live0,
+        [&](int64_t g, int j) {
+            float4 A;
+            float ab2;
+            st_tube_record(a, b, r1, r2, g, &A, &tb[j], &ab2, 0);
+            ta[j] = make_float4(A.x, A.y, A.z, ab2 == 0.0f ? 0.0f : 1.0f / ab2);
+        },
+        [&](int j, int g) {
+            const st_f2 t = st_tube_t_rcp(px, py, pz, ta[j], tb[j], ta[j].w);
+            const st_f2 d2 = st_tube_project(t, px, py, pz, ta[j], tb[j]).d2;
+            if (d2.x < bd0) { bd0 = d2.x; bt0 = t.x; best0 = g; }  // strict: first minimum; NaN / inf never win
+            if (d2.y < bd1) { bd1 = d2.y; bt1 = t.y; best1 = g; }
+        });
     // once per sample: distance, the winner's radius at the projection, the tally terms
     const float nan = __uint_as_float(0x7fc00000u);
     const bool ok0 = live0 && best0 >= 0, ok1 = live1 && best1 >= 0;
     const float d0 = sqrtf(bd0), d1 = sqrtf(bd1);
     float tr0 = nan, tr1 = nan;
-    if (ok0) { const float lo = (1.0f - bt0) * r1[best0], hi = bt0 * r2[best0]; tr0 = lo + hi; }
-    if (ok1) { const float lo = (1.0f - bt1) * r1[best1], hi = bt1 * r2[best1]; tr1 = lo + hi; }
+    if (ok0) tr0 = st_tube_radius(bt0, r1[best0], r2[best0]);
+    if (ok1) tr1 = st_tube_radius(bt1, r1[best1], r2[best1]);
     const float rs0 = live0 ? rad[i0] : 0.0f, rs1 = live1 ? rad[i1] : 0.0f;
     const float ref0 = ref_mode ? tr0 : rs0, ref1 = ref_mode ? tr1 : rs1;
     if (live0) { if (dist) dist[i0] = d0; if (idx) idx[i0] = best0; if (tube_rad) tube_rad[i0] = tr0; }

@@ -23,7 +23,10 @@ def _case(n, m, seed, degenerate=False):
     return pts, a, b, r1, r2
 
 
-@pytest.mark.parametrize("n,m,deg", [(1, 1, False), (700, 37, False), (3000, 1300, False), (500, 90, True)])
+# (511, 512), (513, 513), (1, 1024): the tubes end on one LDS tile edge (512), one past it, on two; an odd n leaves the last lane's
+# second point dead; 513 points cross the workgroup edge at 512
+@pytest.mark.parametrize("n,m,deg", [(1, 1, False), (700, 37, False), (3000, 1300, False), (500, 90, True), (511, 512, False),
+                                     (513, 513, False), (1, 1024, False)])
 def test_nearest_tube_bit_exact(backend, n, m, deg):
     pts, a, b, r1, r2 = _case(n, m, seed=n + m, degenerate=deg)
     vec, idx, rad = qo.nearest_tube(pts, a, b, r1, r2)
@@ -34,6 +37,19 @@ def test_nearest_tube_bit_exact(backend, n, m, deg):
     np.testing.assert_array_equal(gr.cpu().numpy(), rad)
     if deg:
         assert (idx == m // 3).all()
+
+
+def test_first_minimum_wins_across_a_tile_edge(backend):
+    """512 tubes twice over: tube j + 512 scores exactly what tube j does and sits one LDS tile later; the first must win."""
+    pts, a, b, r1, r2 = _case(300, 512, seed=812)
+    a, b, r1, r2 = (np.concatenate([x, x]) for x in (a, b, r1, r2))
+    vec, idx, rad = qo.nearest_tube(pts, a, b, r1, r2)
+    assert (idx < 512).all()
+    t = lambda x: torch.from_numpy(x).to(backend)
+    gv, gi, gr = nearest_tube_device(t(pts), t(a), t(b), t(r1), t(r2))
+    np.testing.assert_array_equal(gi.cpu().numpy(), idx)
+    np.testing.assert_array_equal(gv.cpu().numpy(), vec)
+    np.testing.assert_array_equal(gr.cpu().numpy(), rad)
 
 
 def test_oracle_against_reference_golden():

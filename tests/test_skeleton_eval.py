@@ -95,7 +95,9 @@ def _match_case(n, m):
 
 @pytest.mark.parametrize("T", [1, 10])
 @pytest.mark.parametrize("ref_mode", [0, 1])
-@pytest.mark.parametrize("n,m", [(1, 1), (701, 37), (3000, 1300)])
+# (513, 512), (511, 513): the tubes end on an LDS tile edge and one past it; 513 samples cross the workgroup edge at 512, an odd
+# count leaves the last lane's second sample dead
+@pytest.mark.parametrize("n,m", [(1, 1), (701, 37), (3000, 1300), (513, 512), (511, 513)])
 def test_match_bit_exact(backend, n, m, ref_mode, T):
     pts, rad, a, b, r1, r2, ref = _match_case(n, m)
     want = ref[(ref_mode, T)]
@@ -123,6 +125,19 @@ def test_match_bit_exact(backend, n, m, ref_mode, T):
             assert 0 < hits[0] < hits[-1] < n  # thresholds separate; the NaN sample is in no hit
     if m == 1300:
         assert (want["idx"] >= 512).any() and (want["idx"] < 512).any()  # winners in more than one LDS tile
+
+
+def test_match_first_minimum_wins_across_a_tile_edge(backend):
+    """512 tubes twice over: tube j + 512 is exactly as far as tube j and sits one LDS tile later; the first must win."""
+    pts, rad, a, b, r1, r2, _ = _match_case(300, 512)
+    a, b, r1, r2 = (np.concatenate([x, x]) for x in (a, b, r1, r2))
+    want = eo.match(pts, rad, a, b, r1, r2, THR10, 1)
+    assert (want["idx"] >= 0).all() and (want["idx"] < 512).all()
+    got = match(*_dev(backend, pts, rad, a, b, r1, r2), THR10, 1)
+    np.testing.assert_array_equal(got["idx"].cpu().numpy(), want["idx"])
+    np.testing.assert_array_equal(got["dist"].cpu().numpy(), want["dist"])
+    np.testing.assert_array_equal(got["tube_rad"].cpu().numpy(), want["tube_rad"])
+    np.testing.assert_array_equal(got["hits"].cpu().numpy(), want["hits"])
 
 
 def test_match_argument_checks(backend):

@@ -34,12 +34,16 @@ extern "C" {
  * 108: st_prediction_metrics and its three size queries added (no existing signature changed).
  * 109: the st_render_* calls added (no existing signature changed).
  * 110: st_bridge_components_seg and its size query added (no existing signature changed).
- * 111: st_segment_points_seg and its size query added (no existing signature changed). */
+ * 111: st_segment_points_seg and its size query added (no existing signature changed).
+ * 112: st_brick_pyramid_need, the st_sparse_conv_{mfma,b3,f16}_list_fwd calls, st_pointwise_mlp_heads_keep and st_move_rows_list
+ * added; st_abi_entries(3) added (no existing signature or st_abi_entries value changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
  * st_sample_tree: all ZEROED and written), 1 -> int64 entries of `tuning` (st_skeleton_components_seg: all READ when non-NULL),
- * 2 -> ST_MAX_SEG (clouds per batched call); anything else -> -1 */
+ * 2 -> ST_MAX_SEG (clouds per batched call), 3 -> int64 entries per level of `need_counts_host` (st_brick_pyramid_need: WRITTEN);
+ * anything else -> -1 */
+#define ST_BRICK_NEED_COUNTS 4
 #define ST_SKELETON_STATS_ENTRIES 16
 #define ST_SKELETON_TUNING_ENTRIES 24
 int st_abi_entries(int what);
@@ -78,6 +82,9 @@ int64_t st_spatial_order_workspace_bytes(int64_t n);
 int st_spatial_order(const int32_t* coords, int64_t n, int32_t* order /*[n]*/, void* ws, int64_t ws_bytes, void* stream);
 /* rows of `row_words` 32-bit words moved by a permutation: dst[p] = src[order[p]] (scatter = 0) / dst[order[p]] = src[p] */
 int st_move_rows(const void* src, int row_words, const int32_t* order, int64_t n, void* dst, int scatter, void* stream);
+/* the same move for the n positions list[0 .. n) only (p = list[i]); the other rows of dst are not written */
+int st_move_rows_list(const void* src, int row_words, const int32_t* order, const int32_t* list, int64_t n, void* dst, int scatter,
+                      void* stream);
 int64_t st_strided_workspace_bytes(int64_t n_fine);
 int st_build_strided_outputs(const int32_t* coords, int64_t n, int64_t max_out, int32_t* out_coords,
                              unsigned long long* ckeys, unsigned* cvals, int64_t ccap, int64_t* n_out_host,
@@ -128,6 +135,23 @@ int st_sparse_conv_b3_fwd(const float* x0, int c0, const float* x1, int cin, con
 int st_sparse_conv_f16_fwd(const void* x0, int c0, const void* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
                            const void* w, int cout, const float* scale, const float* shift, const void* residual, int relu,
                            void* y, int in_half, int out_half, const int32_t* row_order, void* stream, int64_t nbr_stride /*0 = n_out*/);
+/* The three matrix-core calls over a LIST of the level's rows (no reference counterpart: the reference evaluates every halo voxel and
+ * throws the result away, model/model_inference.py:97-100).  row_order [n_out] names the rows to compute, y has level_rows rows and
+ * the others are not written.  The kernel instance and row-tile variant are the ones the plain call picks for n_out = level_rows
+ * with (parity != 0) or without a parity order -- never a function of the list -- so a row has the same bits in a list launch and in
+ * a launch of the whole level.  parity != 0: the list is a sub-list of the tagged parity order.  (st_sparse_conv_fwd has one kernel
+ * per shape at every size: it takes a list as its row_order.) */
+int st_sparse_conv_mfma_list_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                                 const float* wp, int cout, const float* scale, const float* shift, const float* residual, int relu,
+                                 float* y, const int32_t* row_order, void* stream, int64_t nbr_stride, int variant, int64_t level_rows,
+                                 int parity);
+int st_sparse_conv_b3_list_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out, const void* wq,
+                               int cout, const float* scale, const float* shift, const float* residual, int relu, float* y,
+                               const int32_t* row_order, void* stream, int64_t nbr_stride, int variant, int64_t level_rows, int parity);
+int st_sparse_conv_f16_list_fwd(const void* x0, int c0, const void* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                                const void* w, int cout, const float* scale, const float* shift, const void* residual, int relu,
+                                void* y, int in_half, int out_half, const int32_t* row_order, void* stream, int64_t nbr_stride,
+                                int64_t level_rows, int parity);
 
 /* ---- rulebooks without hash probes (csrc/brick.hip) ------------------------------------------------
  * replaces, for the network's own forward pass, the per-conv hash build of spconv (model/model_blocks.py:57-70,90-101,134-143)
@@ -144,9 +168,23 @@ int st_brick_pyramid(const int32_t* coords0 /*[n0,4] (batch index, z, y, x), any
                      int32_t* const* subm /*[depth+1] x [27][caps[l]]*/, int32_t* const* down /*[depth] x [27][caps[l+1]]*/,
                      int32_t* const* up /*[depth] x [27][caps[l]]*/, int32_t* const* up_order /*[depth] x [caps[l] + 16]*/,
                      int64_t* counts_host /*[depth+1] rows per level*/, void* ws, int64_t ws_bytes, void* stream);
+/* st_brick_pyramid plus the rows the decoder needs when only the INNER voxels' outputs are kept (blocks with a halo; the rule and its
+ * thresholds a[l] = 0, 1, 2, 2, ...: csrc/st_rule.h).  inner [n0] uint8 in input order, 1 = kept (NULL: no lists, = st_brick_pyramid).
+ * Per level l < depth: need_order[l] = the level's rows with margin <= a[l], then = a[l] + 1, then = a[l] + 2 (brick order inside
+ * each part); up_need[l] = the entries of up_order[l] whose row has margin <= a[l] + 2, tags and parity grouping kept;
+ * need_counts_host[ST_BRICK_NEED_COUNTS * l + 0 .. 2] = the three prefix lengths of need_order[l], [+ 3] = the length of up_need[l].
+ * The counts ride on the call's one read-back.  Same workspace as st_brick_pyramid. */
+int st_brick_pyramid_need(const int32_t* coords0, int64_t n0, int n_blocks, int coord_bound, int depth, const int32_t* blk_seg, int nseg,
+                          const int64_t* caps, int32_t* order0, int32_t* const* coords_out, int32_t* const* subm, int32_t* const* down,
+                          int32_t* const* up, int32_t* const* up_order, int64_t* counts_host, const unsigned char* inner /*[n0] or NULL*/,
+                          int32_t* const* need_order /*[depth] x [caps[l]]*/, int32_t* const* up_need /*[depth] x [caps[l]]*/,
+                          int64_t* need_counts_host /*[ST_BRICK_NEED_COUNTS * depth]*/, void* ws, int64_t ws_bytes, void* stream);
 int st_head_param_floats(void);
 int st_pointwise_mlp_heads(const float* x, int64_t n, const float* params, float* radius, float* direction,
                            float* class_l, float* medial_vector /*nullable*/, int64_t* class_idx /*nullable*/, void* stream);
+/* the heads of the rows with keep[i] != 0 only (keep [n] uint8; NULL: every row): the other rows of x are not read, their outputs are zero */
+int st_pointwise_mlp_heads_keep(const float* x, int64_t n, const unsigned char* keep, const float* params, float* radius, float* direction,
+                                float* class_l, float* medial_vector /*nullable*/, int64_t* class_idx /*nullable*/, void* stream);
 
 /* ---- skeleton stage -------------------------------------------------------------------------------
  * st_medial_points  replaces: Cloud.medial_pts / Cloud.radius, data_types/cloud.py:229-231,254-256

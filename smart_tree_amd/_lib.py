@@ -51,6 +51,14 @@ SIGNATURES = {
     "st_brick_pyramid_workspace_bytes": (I64, [I64, c_int, c_int, c_int, ctypes.POINTER(I64)]),
     "st_brick_pyramid": (c_int, [P, I64, c_int, c_int, c_int, P, c_int, ctypes.POINTER(I64), P, ctypes.POINTER(P), ctypes.POINTER(P),
                                  ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(I64), P, I64, P]),
+    "st_brick_pyramid_need": (c_int, [P, I64, c_int, c_int, c_int, P, c_int, ctypes.POINTER(I64), P, ctypes.POINTER(P), ctypes.POINTER(P),
+                                      ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(I64), P, ctypes.POINTER(P),
+                                      ctypes.POINTER(P), ctypes.POINTER(I64), P, I64, P]),
+    "st_sparse_conv_mfma_list_fwd": (c_int, [P, c_int, P, c_int, P, c_int, I64, P, c_int, P, P, P, c_int, P, P, P, I64, c_int, I64, c_int]),
+    "st_sparse_conv_b3_list_fwd": (c_int, [P, c_int, P, c_int, P, c_int, I64, P, c_int, P, P, P, c_int, P, P, P, I64, c_int, I64, c_int]),
+    "st_sparse_conv_f16_list_fwd": (c_int, [P, c_int, P, c_int, P, c_int, I64, P, c_int, P, P, P, c_int, P, c_int, c_int, P, P, I64, I64, c_int]),
+    "st_pointwise_mlp_heads_keep": (c_int, [P, I64, P, P, P, P, P, P, P, P]),
+    "st_move_rows_list": (c_int, [P, c_int, P, P, I64, P, c_int, P]),
     "st_head_param_floats": (c_int, []),
     "st_pointwise_mlp_heads": (c_int, [P, I64, P, P, P, P, P, P, P]),
     "st_knn_workspace_bytes": (I64, [I64]),
@@ -159,6 +167,7 @@ ENQUEUE_ONLY = frozenset({
     "st_prediction_metrics_tally_ints", "st_prediction_metrics_tally_sums", "st_prediction_metrics_workspace_bytes", "st_prediction_metrics",
     "st_render_workspace_bytes", "st_render_clear", "st_render_points", "st_render_segments", "st_render_resolve",
     "st_bridge_components_workspace_bytes", "st_segment_workspace_bytes", "st_segment_points_seg",
+    "st_sparse_conv_mfma_list_fwd", "st_sparse_conv_b3_list_fwd", "st_sparse_conv_f16_list_fwd", "st_pointwise_mlp_heads_keep", "st_move_rows_list",
 })
 
 

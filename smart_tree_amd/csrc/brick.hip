@@ -25,6 +25,7 @@
 #include "st_common.h"
 #include "st_grid.h"  // ST_MAX_SEG
 #include "st_rule.h"
+#include "smarttree_hip.h"  // ST_BRICK_NEED_COUNTS, and this file's entry points checked against their declarations
 
 #define BK_BLOCK 256
 #define BK_MAX_DEPTH 6
@@ -416,16 +417,162 @@ __global__ void __launch_bounds__(BK_BLOCK) k_bk_updown(const int32_t* coords, c
     if (threadIdx.x < 8 && hist[threadIdx.x]) atomicAdd(&parity_count[threadIdx.x], hist[threadIdx.x]);
 }
 
+// ---- rows the decoder needs (the rule and its derivation: st_rule.h "Which decoder rows ...") -------------------------------------
+// box[0 .. 3 nblk) = lo, box[3 nblk .. 6 nblk) = hi of every block's inner rows (level-0 coordinates; lo > hi: no inner row), from the
+// input rows (coalesced: coordinates and mask are both in input order).  The voxeliser emits a block's rows together, so a wavefront
+// walks BK_BOX_SPAN consecutive groups of 64 rows with a running box per lane for the block it is in and reduces it (shuffles, six
+// atomics) only when the block changes or the span ends; a group that mixes blocks falls back to atomics per row.
+#define BK_BOX_SPAN 32
+__device__ __forceinline__ void bk_box_flush(int* lo, int* hi, int b, int mn[3], int mx[3], int lane) {
+    for (int d = 32; d >= 1; d >>= 1)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            const int o = __shfl_xor(mn[a], d), p = __shfl_xor(mx[a], d);
+            mn[a] = o < mn[a] ? o : mn[a];
+            mx[a] = p > mx[a] ? p : mx[a];
+        }
+    if (lane == 0 && b >= 0)
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            if (mn[a] <= mx[a]) { atomicMin(&lo[3 * b + a], mn[a]); atomicMax(&hi[3 * b + a], mx[a]); }
+        }
+#pragma unroll
+    for (int a = 0; a < 3; a++) { mn[a] = 0x7fffffff; mx[a] = -1; }
+}
+__global__ void __launch_bounds__(BK_BLOCK) k_bk_inner_box(const int32_t* coords0, const unsigned char* inner, int64_t n, int nblk, int lim, int* box,
+                                                           const BkState* st) {
+    if (st->fail) return;
+    const int lane = threadIdx.x & 63;
+    int *lo = box, *hi = box + 3 * nblk;
+    const int64_t first = (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) * (64 * BK_BOX_SPAN);
+    int cur = -1, mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {-1, -1, -1};  // cur is wave-uniform
+    for (int g = 0; g < BK_BOX_SPAN && first + 64 * g < n; g++) {
+        const int64_t i = first + 64 * g + lane;
+        int4 c = make_int4(-1, 0, 0, 0);
+        bool in = false;
+        if (i < n && inner[i] != 0) {
+            c = reinterpret_cast<const int4*>(coords0)[i];
+            in = (unsigned)c.x < (unsigned)nblk && (unsigned)c.y < (unsigned)lim && (unsigned)c.z < (unsigned)lim && (unsigned)c.w < (unsigned)lim;
+        }
+        const unsigned long long who = __ballot(in);
+        if (who == 0ull) continue;
+        if (__ballot(in && c.x != cur) != 0ull) {  // not (only) the block the running box is of
+            if (cur >= 0) bk_box_flush(lo, hi, cur, mn, mx, lane);
+            cur = __shfl(c.x, __ffsll((long long)who) - 1);
+            if (__ballot(in && c.x != cur) != 0ull) {  // the group mixes blocks
+                cur = -1;
+                if (in) {
+                    atomicMin(&lo[3 * c.x], c.y); atomicMax(&hi[3 * c.x], c.y);
+                    atomicMin(&lo[3 * c.x + 1], c.z); atomicMax(&hi[3 * c.x + 1], c.z);
+                    atomicMin(&lo[3 * c.x + 2], c.w); atomicMax(&hi[3 * c.x + 2], c.w);
+                }
+                continue;
+            }
+        }
+        if (in) {
+            mn[0] = c.y < mn[0] ? c.y : mn[0]; mx[0] = c.y > mx[0] ? c.y : mx[0];
+            mn[1] = c.z < mn[1] ? c.z : mn[1]; mx[1] = c.z > mx[1] ? c.z : mx[1];
+            mn[2] = c.w < mn[2] ? c.w : mn[2]; mx[2] = c.w > mx[2] ? c.w : mx[2];
+        }
+    }
+    if (cur >= 0) bk_box_flush(lo, hi, cur, mn, mx, lane);
+}
+
+// A level's two lists by a two-pass stable partition over tiles of BK_BLOCK positions.  Lists 0 .. 2: the rows of margin class 0, 1, 2
+// (need_order = class 0, then 1, then 2, brick order inside a class: a convolution with threshold a[l] + t launches over the prefix
+// that ends with class t); list 3: the entries of the tagged parity order whose row has a class at all (tags and grouping kept).
+// The classes are computed once per level (k_bk_need_class, coalesced) into a byte per row: both passes then read a byte for the
+// row of their position and gather a byte for the row their entry of the parity order names.
+#define BK_NEED_LISTS (ST_RULE_NEED_CLASSES + 1)
+static_assert(BK_NEED_LISTS == ST_BRICK_NEED_COUNTS, "header and library disagree about the need counts per level");
+__global__ void __launch_bounds__(BK_BLOCK) k_bk_need_class(const int32_t* coords, const int64_t* n_dev, int64_t cap, const int* box, int nblk,
+                                                            int level, unsigned char* cls, const BkState* st) {
+    if (st->fail) return;
+    const int64_t n = *n_dev < cap ? *n_dev : cap;
+    BK_LOOP(row, n) {
+        const int4 c = reinterpret_cast<const int4*>(coords)[row];
+        const int cc[3] = {c.y, c.z, c.w};
+        cls[row] = (unsigned char)((unsigned)c.x < (unsigned)nblk ? st_rule_need_class(cc, box + 3 * c.x, box + 3 * nblk + 3 * c.x, level)
+                                                                  : ST_RULE_NEED_CLASSES);
+    }
+}
+// what position `pos` of the level contributes: cls = class of row pos, keep / entry = whether entry pos of the parity order stays
+__device__ __forceinline__ void bk_need_classify(const unsigned char* cls8, int64_t n, int64_t pos, const int32_t* up_order, int* cls, bool* keep,
+                                                 int32_t* entry) {
+    *cls = ST_RULE_NEED_CLASSES;
+    *keep = false;
+    *entry = 0;
+    if (pos >= n) return;
+    *cls = cls8[pos];
+    *entry = up_order[pos];
+    const int64_t row = st_rule_row(*entry);
+    *keep = row < n && cls8[row] < ST_RULE_NEED_CLASSES;
+}
+// PASS 1: cnt[list * ntiles + tile] (zeroed before; scanned afterwards as ONE array, so a list starts where the one before ends)
+__global__ void __launch_bounds__(BK_BLOCK) k_bk_need_count(const unsigned char* cls8, const int64_t* n_dev, int64_t cap, const int32_t* up_order,
+                                                            uint32_t* cnt, int64_t ntiles, const BkState* st) {
+    if (st->fail) return;
+    const int64_t n = *n_dev < cap ? *n_dev : cap, pos = (int64_t)blockIdx.x * BK_BLOCK + threadIdx.x;
+    int cls;
+    bool keep;
+    int32_t entry;
+    bk_need_classify(cls8, n, pos, up_order, &cls, &keep, &entry);
+#pragma unroll
+    for (int q = 0; q < BK_NEED_LISTS; q++) {
+        const unsigned long long b = __ballot(q < ST_RULE_NEED_CLASSES ? cls == q : keep);
+        if ((threadIdx.x & 63) == 0 && b != 0ull) atomicAdd(&cnt[q * ntiles + blockIdx.x], (uint32_t)__popcll(b));
+    }
+}
+// PASS 2: base = the scanned counts ([BK_NEED_LISTS * ntiles + 1], the last entry = all four lists together); counts [4]: the three
+// prefix lengths of need_order and the length of up_need
+__global__ void __launch_bounds__(BK_BLOCK) k_bk_need_emit(const unsigned char* cls8, const int64_t* n_dev, int64_t cap, const int32_t* up_order,
+                                                           const uint32_t* base, int64_t ntiles,
+                                                           int32_t* need_order, int32_t* up_need, int64_t* counts, const BkState* st) {
+    __shared__ uint32_t wcnt[BK_BLOCK / 64][BK_NEED_LISTS];
+    if (st->fail) return;
+    const int64_t n = *n_dev < cap ? *n_dev : cap, pos = (int64_t)blockIdx.x * BK_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int cls;
+    bool keep;
+    int32_t entry;
+    bk_need_classify(cls8, n, pos, up_order, &cls, &keep, &entry);
+    uint32_t rank[BK_NEED_LISTS];
+#pragma unroll
+    for (int q = 0; q < BK_NEED_LISTS; q++) {
+        const unsigned long long b = __ballot(q < ST_RULE_NEED_CLASSES ? cls == q : keep);
+        rank[q] = (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) wcnt[wave][q] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    const uint32_t up0 = base[ST_RULE_NEED_CLASSES * ntiles];  // where list 3 starts = the length of need_order
+#pragma unroll
+    for (int q = 0; q < BK_NEED_LISTS; q++) {
+        if (q < ST_RULE_NEED_CLASSES ? cls != q : !keep) continue;
+        int64_t at = (int64_t)base[q * ntiles + blockIdx.x] + rank[q];
+        for (int w = 0; w < wave; w++) at += wcnt[w][q];
+        if (q < ST_RULE_NEED_CLASSES) { if (at < n) need_order[at] = (int32_t)pos; }
+        else if (at - up0 < n) up_need[at - up0] = entry;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int q = 0; q < ST_RULE_NEED_CLASSES; q++) counts[q] = base[(q + 1) * ntiles];
+        counts[ST_RULE_NEED_CLASSES] = (int64_t)base[BK_NEED_LISTS * ntiles] - up0;
+    }
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 struct BkPlan {
     int depth;
     int mb[BK_MAX_DEPTH + 1];
     int64_t ntab[BK_MAX_DEPTH + 1], slot_cap[BK_MAX_DEPTH + 1];
+    int n_blocks;
+    int64_t cap_max;  // the largest row capacity of a level
 };
 
 static bool bk_plan(int64_t n0, int n_blocks, int coord_bound, int depth, const int64_t* caps, BkPlan* P) {
     if (depth < 0 || depth > BK_MAX_DEPTH || n_blocks < 1 || coord_bound < 1) return false;
     P->depth = depth;
+    P->n_blocks = n_blocks;
+    P->cap_max = 1;
     int bound = coord_bound;  // coordinates of level l are < bound_l
     for (int l = 0; l <= depth; l++) {
         int nb = (bound + 7) / 8, mb = 0;
@@ -438,14 +585,22 @@ static bool bk_plan(int64_t n0, int n_blocks, int coord_bound, int depth, const 
         // the level's row capacity (level 0: caps[0], which may exceed n0) must fit the tagged row order
         if ((l == 0 && caps && caps[0] > cap ? caps[0] : cap) >= ST_RULE_ROW_LIMIT) return false;
         P->slot_cap[l] = cap < P->ntab[l] ? cap : P->ntab[l];
+        const int64_t rows = l == 0 && caps && caps[0] > cap ? caps[0] : cap;
+        if (rows > P->cap_max) P->cap_max = rows;
         bound = (bound - 1) / 2 + 1;
     }
     return true;
 }
 
+#define BK_COUNTS (2 * (BK_MAX_DEPTH + 1) + BK_NEED_LISTS * BK_MAX_DEPTH)
+static inline int64_t bk_need_tiles(int64_t cap) { return st_div_up(cap > 0 ? cap : 1, BK_BLOCK); }
+
 struct BkLayout {
     BkState* st;
-    int64_t* counts;    // [2 * (depth + 1)]: n_slots, n_vox per level
+    int64_t* counts;    // [BK_COUNTS]: n_slots, n_vox per level, then per level the four lengths of k_bk_need_emit
+    int* box;           // [6 * n_blocks] inner box of every block (k_bk_inner_box)
+    unsigned char* need_cls;  // [cap_max] margin class of every row of the level at hand
+    uint32_t* need_cnt; // [BK_NEED_LISTS * tiles + 1] per-tile counts of the need lists, then their exclusive prefix
     uint32_t* p[BK_MAX_DEPTH + 1];
     BkRec* rec[BK_MAX_DEPTH + 1];
     uint32_t* base[BK_MAX_DEPTH + 1];
@@ -455,8 +610,12 @@ struct BkLayout {
 
 static void bk_layout(StArena& a, const BkPlan& P, BkLayout* Y) {
     Y->st = a.take<BkState>(1);
-    Y->counts = a.take<int64_t>(2 * (BK_MAX_DEPTH + 1));
-    int64_t scan_n = 1;
+    Y->counts = a.take<int64_t>(BK_COUNTS);
+    Y->box = a.take<int>(6 * (int64_t)P.n_blocks);
+    const int64_t need_n = BK_NEED_LISTS * bk_need_tiles(P.cap_max) + 1;
+    Y->need_cls = a.take<unsigned char>(P.cap_max);
+    Y->need_cnt = a.take<uint32_t>(need_n);
+    int64_t scan_n = need_n;
     for (int l = 0; l <= P.depth; l++) {
         Y->p[l] = a.take<uint32_t>(P.ntab[l] + 1);
         Y->rec[l] = a.take<BkRec>(P.slot_cap[l]);
@@ -487,12 +646,20 @@ extern "C" int64_t st_brick_pyramid_workspace_bytes(int64_t n0, int n_blocks, in
 // out: order0 [n0] (row p of level 0 holds input voxel order0[p]); coords_out[l] [caps[l],4]; subm[l] [27][caps[l]];
 //   down[l] [27][caps[l+1]]; up[l] [27][caps[l]]; up_order[l] [caps[l] + 16]; counts_host [depth + 1] rows per level (ONE
 //   device-to-host copy at the end of the call).
-extern "C" int st_brick_pyramid(const int32_t* coords0, int64_t n0, int n_blocks, int coord_bound, int depth, const int32_t* blk_seg,
-                                int nseg, const int64_t* caps, int32_t* order0, int32_t* const* coords_out, int32_t* const* subm,
-                                int32_t* const* down, int32_t* const* up, int32_t* const* up_order, int64_t* counts_host, void* ws,
-                                int64_t ws_bytes, void* stream_) {
+// st_brick_pyramid_need: the same, plus the rows the decoder needs when only the INNER voxels' outputs are kept (st_rule.h).
+//   inner [n0] uint8, input order: 1 = the voxel's output is kept.  Per level l < depth: need_order[l] [caps[l]] = the level's rows of
+//   margin class 0, then 1, then 2 (brick order inside a class); up_need[l] [caps[l]] = the entries of up_order[l] whose row has a
+//   class (tags and parity grouping kept); need_counts_host [4 * depth]: per level the three prefix lengths of need_order (rows with
+//   margin <= a[l], a[l] + 1, a[l] + 2) and the length of up_need -- they ride on the same read-back.  inner == NULL: no lists.
+extern "C" int st_brick_pyramid_need(const int32_t* coords0, int64_t n0, int n_blocks, int coord_bound, int depth, const int32_t* blk_seg,
+                                     int nseg, const int64_t* caps, int32_t* order0, int32_t* const* coords_out, int32_t* const* subm,
+                                     int32_t* const* down, int32_t* const* up, int32_t* const* up_order, int64_t* counts_host,
+                                     const unsigned char* inner, int32_t* const* need_order, int32_t* const* up_need,
+                                     int64_t* need_counts_host, void* ws, int64_t ws_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     for (int l = 0; l <= depth && l <= BK_MAX_DEPTH; l++) counts_host[l] = 0;
+    ST_REQUIRE(!inner || (need_order && up_need && need_counts_host), "brick pyramid: an inner mask needs the arrays of the need lists");
+    for (int i = 0; inner && i < BK_NEED_LISTS * depth && i < BK_NEED_LISTS * BK_MAX_DEPTH; i++) need_counts_host[i] = 0;
     if (n0 <= 0) return ST_OK;
     ST_REQUIRE(nseg >= 1 && nseg <= ST_MAX_SEG && (nseg == 1 || blk_seg), "brick pyramid: 1 <= clouds per batch <= %d", ST_MAX_SEG);
     ST_REQUIRE(caps && caps[0] >= n0, "brick pyramid: caps[0] must hold the input voxels");
@@ -507,7 +674,7 @@ extern "C" int st_brick_pyramid(const int32_t* coords0, int64_t n0, int n_blocks
         return ST_ERR_WORKSPACE;
     }
     (void)hipMemsetAsync(Y.st, 0, sizeof(BkState), stream);
-    (void)hipMemsetAsync(Y.counts, 0, 2 * (BK_MAX_DEPTH + 1) * sizeof(int64_t), stream);
+    (void)hipMemsetAsync(Y.counts, 0, BK_COUNTS * sizeof(int64_t), stream);
     BkLevel L[BK_MAX_DEPTH + 1];
     for (int l = 0; l <= depth; l++) {
         L[l].mb = P.mb[l]; L[l].mt = 1u << (3 * P.mb[l]); L[l].ntab = P.ntab[l]; L[l].p = Y.p[l]; L[l].rec = Y.rec[l];
@@ -551,8 +718,27 @@ extern "C" int st_brick_pyramid(const int32_t* coords0, int64_t n0, int n_blocks
                            L[l + 1], (const BkState*)Y.st, l, blk_seg, (const int64_t*)L[l + 1].n_vox, cap_c, up[l], down[l], pc);
         st_rule_parity_order(coords_out[l], cap, L[l].n_vox, &Y.st->fail, pc, up_order[l], stream);
     }
+    // ---- the need lists, once every level's rows are known: the inner boxes, then per level classes, count, scan, emit
+    if (inner) {
+        (void)hipMemsetAsync(Y.box, 0x7f, 3 * (size_t)n_blocks * sizeof(int), stream);                  // lo: huge
+        (void)hipMemsetAsync(Y.box + 3 * (int64_t)n_blocks, 0xff, 3 * (size_t)n_blocks * sizeof(int), stream);  // hi: -1
+        hipLaunchKernelGGL(k_bk_inner_box, dim3((unsigned)st_div_up(n0, BK_BLOCK * BK_BOX_SPAN)), dim3(BK_BLOCK), 0, stream, coords0, inner, n0,
+                           n_blocks, 8 << P.mb[0], Y.box, (const BkState*)Y.st);
+        for (int l = 0; l < depth; l++) {
+            const int64_t cap = caps[l], ntiles = bk_need_tiles(cap), cnt_n = BK_NEED_LISTS * ntiles + 1;
+            (void)hipMemsetAsync(Y.need_cnt, 0, cnt_n * sizeof(uint32_t), stream);
+            hipLaunchKernelGGL(k_bk_need_class, dim3(bk_grid(cap)), dim3(BK_BLOCK), 0, stream, (const int32_t*)coords_out[l], (const int64_t*)L[l].n_vox, cap,
+                               (const int*)Y.box, n_blocks, l, Y.need_cls, (const BkState*)Y.st);
+            hipLaunchKernelGGL(k_bk_need_count, dim3((unsigned)ntiles), dim3(BK_BLOCK), 0, stream, (const unsigned char*)Y.need_cls,
+                               (const int64_t*)L[l].n_vox, cap, (const int32_t*)up_order[l], Y.need_cnt, ntiles, (const BkState*)Y.st);
+            ST_TRY(st_exclusive_scan_u32(Y.need_cnt, Y.need_cnt, cnt_n, nullptr, Y.scan_ws, Y.scan_bytes, stream));
+            hipLaunchKernelGGL(k_bk_need_emit, dim3((unsigned)ntiles), dim3(BK_BLOCK), 0, stream, (const unsigned char*)Y.need_cls,
+                               (const int64_t*)L[l].n_vox, cap, (const int32_t*)up_order[l], (const uint32_t*)Y.need_cnt, ntiles, need_order[l],
+                               up_need[l], Y.counts + 2 * (BK_MAX_DEPTH + 1) + BK_NEED_LISTS * l, (const BkState*)Y.st);
+        }
+    }
     // the ONE read-back: rows per level + the fail flags
-    struct { int64_t counts[2 * (BK_MAX_DEPTH + 1)]; } hc;
+    struct { int64_t counts[BK_COUNTS]; } hc;
     unsigned hfail = 0;
     (void)hipMemcpyAsync(&hc, Y.counts, sizeof(hc), hipMemcpyDeviceToHost, stream);
     (void)hipMemcpyAsync(&hfail, &Y.st->fail, sizeof(unsigned), hipMemcpyDeviceToHost, stream);
@@ -568,5 +754,14 @@ extern "C" int st_brick_pyramid(const int32_t* coords0, int64_t n0, int n_blocks
     }
     ST_REQUIRE(hc.counts[1] == n0, "brick pyramid: %lld distinct voxels among %lld input rows (duplicate coordinates)", (long long)hc.counts[1],
                (long long)n0);
+    for (int i = 0; inner && i < BK_NEED_LISTS * depth; i++) need_counts_host[i] = hc.counts[2 * (BK_MAX_DEPTH + 1) + i];
     return ST_OK;
+}
+
+extern "C" int st_brick_pyramid(const int32_t* coords0, int64_t n0, int n_blocks, int coord_bound, int depth, const int32_t* blk_seg,
+                                int nseg, const int64_t* caps, int32_t* order0, int32_t* const* coords_out, int32_t* const* subm,
+                                int32_t* const* down, int32_t* const* up, int32_t* const* up_order, int64_t* counts_host, void* ws,
+                                int64_t ws_bytes, void* stream_) {
+    return st_brick_pyramid_need(coords0, n0, n_blocks, coord_bound, depth, blk_seg, nseg, caps, order0, coords_out, subm, down, up, up_order,
+                                 counts_host, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, stream_);
 }

@@ -434,11 +434,11 @@ extern "C" int st_spatial_order(const int32_t* coords, int64_t n, int32_t* order
 // 12- and 16-byte rows at a tenth of the HBM rate).
 template <int VEC>
 __global__ void __launch_bounds__(RB_BLOCK) k_rb_move_rows(const uint32_t* __restrict__ src, int row_words, const int32_t* __restrict__ order,
-                                                           int64_t n, uint32_t* __restrict__ dst, int scatter) {
+                                                           int64_t n, uint32_t* __restrict__ dst, int scatter, const int32_t* __restrict__ list) {
     const int per_row = row_words / VEC;
     const int64_t total = n * per_row;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t p = t / per_row;
+        const int64_t p = list ? (int64_t)list[t / per_row] : t / per_row;  // the list form moves positions list[0 .. n) only
         const int c = (int)(t % per_row) * VEC;
         const int64_t o = order[p];
         const int64_t from = (scatter ? p : o) * row_words + c, to = (scatter ? o : p) * row_words + c;
@@ -447,7 +447,9 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_move_rows(const uint32_t* __res
     }
 }
 
-extern "C" int st_move_rows(const void* src, int row_words, const int32_t* order, int64_t n, void* dst, int scatter, void* stream_) {
+// st_move_rows_list: the same move for the n positions list[0 .. n) of the order only; the other rows of dst are not written.
+extern "C" int st_move_rows_list(const void* src, int row_words, const int32_t* order, const int32_t* list, int64_t n, void* dst, int scatter,
+                                 void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (n <= 0) return ST_OK;
     ST_REQUIRE(row_words >= 1 && row_words <= 256, "move_rows: rows of 1..256 words");
@@ -455,10 +457,14 @@ extern "C" int st_move_rows(const void* src, int row_words, const int32_t* order
     const int64_t total = n * (vec ? row_words / 4 : row_words);
     if (vec)
         hipLaunchKernelGGL((k_rb_move_rows<4>), dim3(rb_grid(total)), dim3(RB_BLOCK), 0, stream, (const uint32_t*)src, row_words, order, n,
-                           (uint32_t*)dst, scatter);
+                           (uint32_t*)dst, scatter, list);
     else
         hipLaunchKernelGGL((k_rb_move_rows<1>), dim3(rb_grid(total)), dim3(RB_BLOCK), 0, stream, (const uint32_t*)src, row_words, order, n,
-                           (uint32_t*)dst, scatter);
+                           (uint32_t*)dst, scatter, list);
     ST_CHECK_LAUNCH();
     return ST_OK;
+}
+
+extern "C" int st_move_rows(const void* src, int row_words, const int32_t* order, int64_t n, void* dst, int scatter, void* stream_) {
+    return st_move_rows_list(src, row_words, order, nullptr, n, dst, scatter, stream_);
 }

@@ -1784,7 +1784,7 @@ struct SkHelperLease {  // returned on every way out of the call
 // lengths of the caller-provided int64 arrays this build reads / writes (include/smarttree_hip.h: st_abi_entries)
 static_assert(ST_TUNE_ENTRIES == ST_SKELETON_TUNING_ENTRIES, "header and library disagree about the tuning array");
 extern "C" int st_abi_entries(int what) {
-    return what == 0 ? ST_SKELETON_STATS_ENTRIES : (what == 1 ? ST_SKELETON_TUNING_ENTRIES : (what == 2 ? ST_MAX_SEG : -1));
+    return what == 0 ? ST_SKELETON_STATS_ENTRIES : (what == 1 ? ST_SKELETON_TUNING_ENTRIES : (what == 2 ? ST_MAX_SEG : (what == 3 ? ST_BRICK_NEED_COUNTS : -1)));
 }
 
 extern "C" int64_t st_skeleton_workspace_bytes_seg(int64_t m, int64_t n_comp, int nseg) {

@@ -183,11 +183,19 @@ struct ConvArgs {
     void* y;
     const int32_t* row_order;
     hipStream_t stream;
+    // What the choice of a kernel instance and row-tile variant is keyed on.  A launch over a LIST of rows (row_order names fewer rows
+    // than the level has) must run the instance the whole level runs, so that a row has the same bits either way: level_rows = rows
+    // of the whole level, parity = the layer's launch order is the tagged parity order (an inverse convolution), not just any list.
+    // The plain entry points set them from n_out and row_order (conv_check_args).
+    int64_t level_rows = 0;
+    bool parity = false;
 };
 
 // The checks the four entry points share; nstride arrives as the caller's nbr_stride (0 = n_out).
 static int conv_check_args(ConvArgs* a, int cin) {
     if (a->nstride <= 0) a->nstride = a->n_out;
+    if (a->level_rows <= 0) { a->level_rows = a->n_out; a->parity = a->row_order != nullptr; }
+    ST_REQUIRE(a->level_rows >= a->n_out && (a->level_rows == a->n_out || a->row_order != nullptr), "conv: a launch over fewer rows than the level has needs their list");
     ST_REQUIRE(a->K >= 1 && (a->nbr != nullptr || a->K == 1), "conv: a NULL neighbour table means pointwise (K = 1)");
     ST_REQUIRE(a->c0 > 0 && a->c0 <= cin && (a->c0 == cin || a->x1 != nullptr), "conv: bad concat split");
     ST_REQUIRE((a->scale == nullptr) == (a->shift == nullptr), "conv: scale and shift go together");
@@ -455,7 +463,7 @@ static int mf_launch(mf_kernel_t<T, W> kernel, int rt, const ConvArgs& a) {
 // launch set, profiles/r03_conv_layers_b3.txt): two row tiles per wavefront (each B fragment feeds two tiles) win from ~56k rows
 // on, for the parity-ordered inverse convs from ~300k; below, one tile per wavefront gives the chip twice the wavefronts.  Both
 // compute a row with the same instruction sequence: same bits.
-static int conv_row_tiles(const ConvArgs& a) { return a.n_out >= (a.row_order == nullptr ? 56000 : 300000) ? 2 : 1; }
+static int conv_row_tiles(const ConvArgs& a) { return a.level_rows >= (!a.parity ? 56000 : 300000) ? 2 : 1; }
 
 template <int CIN, int COUT>
 static int conv_launch_mfma(const ConvArgs& a, int v) {
@@ -464,7 +472,7 @@ static int conv_launch_mfma(const ConvArgs& a, int v) {
     // straight from L2 wins while a level has too few rows to fill the chip (one cloud: <= 90k rows below level 0) and for the
     // parity-ordered inverse convs; from ~150k rows on (a batch of clouds, the 5M-point cloud) two row tiles per wave with
     // W_k staged once per workgroup in LDS is 5-20 % faster (B fragments reused, a quarter of the weight traffic from L2)
-    if (v == 0) v = (a.row_order == nullptr && a.n_out >= 150000) ? 18 : 1;
+    if (v == 0) v = (!a.parity && a.level_rows >= 150000) ? 18 : 1;
     switch (v) {
         case 1: return mf_launch(k_sparse_conv_mfma<CIN, COUT, 1, false>, 1, a);
         case 2: return mf_launch(k_sparse_conv_mfma<CIN, COUT, 2, false>, 2, a);
@@ -477,10 +485,14 @@ static int conv_launch_mfma(const ConvArgs& a, int v) {
 // Same contract as st_sparse_conv_mfma_fwd with the weights as three bf16 planes (see above; smart_tree_amd/model/sparse_ops.py
 // b3_weight: for Cin = 16 the pair layout [ceil(K/2)][3][4][Cout][8]).  Needs Cin % 32 == 0, Cout % 16 == 0 and a concat split
 // that is a multiple of 8.  variant: 0 = by size, 1 / 2 = row tiles per wavefront.
-extern "C" int st_sparse_conv_b3_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
-                                     const void* wq, int cout, const float* scale, const float* shift, const float* residual,
-                                     int relu, float* y, const int32_t* row_order, void* stream_, int64_t nbr_stride, int variant) {
-    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, wq, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_};
+// st_sparse_conv_*_list_fwd: the same call over a LIST of the level's rows.  row_order [n_out] names the rows to compute (tags allowed),
+// y has level_rows rows and the others are not written; parity != 0: the list is a sub-list of the layer's tagged parity order.  The
+// kernel instance and row-tile variant are those of the plain call with n_out = level_rows and (parity ? an order : none).
+extern "C" int st_sparse_conv_b3_list_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                                          const void* wq, int cout, const float* scale, const float* shift, const float* residual,
+                                          int relu, float* y, const int32_t* row_order, void* stream_, int64_t nbr_stride, int variant,
+                                          int64_t level_rows, int parity) {
+    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, wq, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_, level_rows, parity != 0};
     ST_TRY(conv_check_args(&a, cin));
     ST_REQUIRE((cin % 32 == 0 || (cin == 16 && c0 == cin)) && cout % 16 == 0 && c0 % 8 == 0,
                "conv(b3): Cin % 32 (or Cin = 16 without concat), Cout % 16 and a concat split % 8 are required");
@@ -499,6 +511,12 @@ extern "C" int st_sparse_conv_b3_fwd(const float* x0, int c0, const float* x1, i
     st_set_error("conv(b3): no kernel instance for cin=%d cout=%d", cin, cout);
     return ST_ERR_INVALID;
 }
+extern "C" int st_sparse_conv_b3_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                                     const void* wq, int cout, const float* scale, const float* shift, const float* residual,
+                                     int relu, float* y, const int32_t* row_order, void* stream_, int64_t nbr_stride, int variant) {
+    return st_sparse_conv_b3_list_fwd(x0, c0, x1, cin, nbr, K, n_out, wq, cout, scale, shift, residual, relu, y, row_order, stream_, nbr_stride,
+                                      variant, 0, 0);
+}
 
 // Half-precision storage variants of the two calls above (config 5).  in_half / out_half say which side is fp16:
 //   both      -> the f16 matrix-core kernels (Cin % 32 == 0, or Cin = 16 without concat and Cout 16 / 32); weights =
@@ -506,11 +524,11 @@ extern "C" int st_sparse_conv_b3_fwd(const float* x0, int c0, const float* x1, i
 //   exactly one -> the float32 kernel with a converting load or store (the 8 -> 16 "down" and 16 -> 8 "up" convs
 //                between the float32 level 0 and the half-precision levels below); weights [K][cin][cout] float32,
 //                no residual
-extern "C" int st_sparse_conv_f16_fwd(const void* x0, int c0, const void* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
-                                      const void* w, int cout, const float* scale, const float* shift, const void* residual,
-                                      int relu, void* y, int in_half, int out_half, const int32_t* row_order, void* stream_,
-                                      int64_t nbr_stride) {
-    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, w, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_};
+extern "C" int st_sparse_conv_f16_list_fwd(const void* x0, int c0, const void* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                                           const void* w, int cout, const float* scale, const float* shift, const void* residual,
+                                           int relu, void* y, int in_half, int out_half, const int32_t* row_order, void* stream_,
+                                           int64_t nbr_stride, int64_t level_rows, int parity) {
+    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, w, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_, level_rows, parity != 0};
     ST_TRY(conv_check_args(&a, cin));
     ST_REQUIRE(in_half || out_half, "conv(f16): neither side is half precision -- use st_sparse_conv_fwd");
     if (n_out <= 0) return ST_OK;
@@ -542,14 +560,21 @@ extern "C" int st_sparse_conv_f16_fwd(const void* x0, int c0, const void* x1, in
     st_set_error("conv(f16): no converting kernel instance for cin=%d cout=%d", cin, cout);
     return ST_ERR_INVALID;
 }
+extern "C" int st_sparse_conv_f16_fwd(const void* x0, int c0, const void* x1, int cin, const int32_t* nbr, int K, int64_t n_out,
+                                      const void* w, int cout, const float* scale, const float* shift, const void* residual,
+                                      int relu, void* y, int in_half, int out_half, const int32_t* row_order, void* stream_,
+                                      int64_t nbr_stride) {
+    return st_sparse_conv_f16_list_fwd(x0, c0, x1, cin, nbr, K, n_out, w, cout, scale, shift, residual, relu, y, in_half, out_half, row_order,
+                                       stream_, nbr_stride, 0, 0);
+}
 
 // Same contract as st_sparse_conv_fwd, weights in the MFMA order wp[K][Cin/16][4][Cout][4] (see above).
 // Needs Cin, Cout multiples of 16 and a concat split that is a multiple of 16 (or no concat).
-extern "C" int st_sparse_conv_mfma_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K,
-                                       int64_t n_out, const float* wp, int cout, const float* scale, const float* shift,
-                                       const float* residual, int relu, float* y, const int32_t* row_order, void* stream_,
-                                       int64_t nbr_stride, int variant) {
-    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, wp, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_};
+extern "C" int st_sparse_conv_mfma_list_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K,
+                                            int64_t n_out, const float* wp, int cout, const float* scale, const float* shift,
+                                            const float* residual, int relu, float* y, const int32_t* row_order, void* stream_,
+                                            int64_t nbr_stride, int variant, int64_t level_rows, int parity) {
+    ConvArgs a = {x0, c0, x1, nbr, K, n_out, nbr_stride, wp, scale, shift, residual, relu, y, row_order, (hipStream_t)stream_, level_rows, parity != 0};
     ST_TRY(conv_check_args(&a, cin));
     ST_REQUIRE(cin % 16 == 0 && cout % 16 == 0 && c0 % 16 == 0, "conv(mfma): channels and concat split must be multiples of 16");
     if (n_out <= 0) return ST_OK;
@@ -565,6 +590,13 @@ extern "C" int st_sparse_conv_mfma_fwd(const float* x0, int c0, const float* x1,
 #undef MFMA_CASE
     st_set_error("conv(mfma): no kernel instance for cin=%d cout=%d", cin, cout);
     return ST_ERR_INVALID;
+}
+extern "C" int st_sparse_conv_mfma_fwd(const float* x0, int c0, const float* x1, int cin, const int32_t* nbr, int K,
+                                       int64_t n_out, const float* wp, int cout, const float* scale, const float* shift,
+                                       const float* residual, int relu, float* y, const int32_t* row_order, void* stream_,
+                                       int64_t nbr_stride, int variant) {
+    return st_sparse_conv_mfma_list_fwd(x0, c0, x1, cin, nbr, K, n_out, wp, cout, scale, shift, residual, relu, y, row_order, stream_, nbr_stride,
+                                        variant, 0, 0);
 }
 
 // x = cat(x0[:, :c0], x1[:, :cin-c0]) (x1 may be NULL when c0 == cin); w [K][cin][cout];
@@ -656,9 +688,17 @@ __device__ __forceinline__ void head_eval(const float* __restrict__ p, const flo
 __global__ void __launch_bounds__(CONV_BLOCK) k_heads(const float* __restrict__ x, int64_t n, const float* __restrict__ params,
                                                       float* __restrict__ radius, float* __restrict__ direction,
                                                       float* __restrict__ class_l, float* __restrict__ medial_vector,
-                                                      int64_t* __restrict__ class_idx) {
+                                                      int64_t* __restrict__ class_idx, const unsigned char* __restrict__ keep) {
     int64_t i = (int64_t)blockIdx.x * CONV_BLOCK + threadIdx.x;
     if (i >= n) return;
+    if (keep && !keep[i]) {  // a row nobody keeps: x[i] may never have been computed -- it is not read, the outputs are zero
+        radius[i] = 0.0f;
+        direction[3 * i] = 0.0f; direction[3 * i + 1] = 0.0f; direction[3 * i + 2] = 0.0f;
+        class_l[2 * i] = 0.0f; class_l[2 * i + 1] = 0.0f;
+        if (medial_vector) { medial_vector[3 * i] = 0.0f; medial_vector[3 * i + 1] = 0.0f; medial_vector[3 * i + 2] = 0.0f; }
+        if (class_idx) class_idx[i] = 0;
+        return;
+    }
     const float4 a = *reinterpret_cast<const float4*>(x + i * 8);
     const float4 b = *reinterpret_cast<const float4*>(x + i * 8 + 4);
     const float xv[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
@@ -681,12 +721,20 @@ __global__ void __launch_bounds__(CONV_BLOCK) k_heads(const float* __restrict__ 
 
 extern "C" int st_head_param_floats(void) { return 3 * HEAD_STRIDE; }
 
-extern "C" int st_pointwise_mlp_heads(const float* x, int64_t n, const float* params, float* radius, float* direction,
-                                      float* class_l, float* medial_vector, int64_t* class_idx, void* stream_) {
+// The heads of the rows with keep[i] != 0 (keep [n] uint8, NULL: every row); the other rows of x are not read and every output of
+// theirs is zero.  (A skip test and not a row list: the kept rows are in the order of x, so loads and stores stay coalesced -- over a
+// gathered list this kernel took three times as long as over every row.)
+extern "C" int st_pointwise_mlp_heads_keep(const float* x, int64_t n, const unsigned char* keep, const float* params, float* radius,
+                                           float* direction, float* class_l, float* medial_vector, int64_t* class_idx, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (n <= 0) return ST_OK;
     hipLaunchKernelGGL(k_heads, dim3((unsigned)st_div_up(n, CONV_BLOCK)), dim3(CONV_BLOCK), 0, stream, x, n, params, radius,
-                       direction, class_l, medial_vector, class_idx);
+                       direction, class_l, medial_vector, class_idx, keep);
     ST_CHECK_LAUNCH();
     return ST_OK;
+}
+
+extern "C" int st_pointwise_mlp_heads(const float* x, int64_t n, const float* params, float* radius, float* direction,
+                                      float* class_l, float* medial_vector, int64_t* class_idx, void* stream_) {
+    return st_pointwise_mlp_heads_keep(x, n, nullptr, params, radius, direction, class_l, medial_vector, class_idx, stream_);
 }

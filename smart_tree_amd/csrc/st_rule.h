@@ -58,6 +58,49 @@ __device__ __forceinline__ uint32_t st_rule_live_offsets(int32_t entry, int K) {
 void st_rule_parity_order(const int32_t* coords, int64_t cap, const int64_t* n_dev, const unsigned* fail, uint32_t* pc, int32_t* order,
                           hipStream_t stream);
 
+// Which decoder rows a consumer of the INNER rows needs (block mode: every block carries a halo whose outputs are thrown away).
+// Eval-mode BatchNorm is a per-channel affine, so an output row is a pure function of the rows its table names: a row nothing
+// kept depends on can be left out without changing a bit of the rows that are kept.  The rule is conservative and reads no table:
+//   box     per block (batch index) the bounding box [lo, hi] of its inner rows' level-0 coordinates; one level down the box is
+//           [lo >> 1, (hi + 1) >> 1] (st_rule_need_box).  A block without an inner row has no box: none of its rows is needed.
+//   margin  of a row at level l: its Chebyshev distance, in level-l voxels, from its block's level-l box (0 inside).
+//   subm    in = out + (k - 1): an output at margin m reads inputs at margin <= m + 1.
+//   inverse a fine c pairs with coarse o where 2 o - 1 + k = c, so o is floor(c / 2) or ceil(c / 2).  With lo - m <= c <= hi + m:
+//           o >= floor((lo - m) / 2) >= (lo >> 1) - ceil(m / 2) and o <= ceil((hi + m) / 2) <= ((hi + 1) >> 1) + ceil(m / 2) --
+//           coarse margin <= ceil(m / 2) against the halved box.
+//   clip    the clip at the cloud's extent (st_rule_omax) only removes pairs.
+// Walking a level's decoder backwards from the rows its consumer keeps (margin <= a[l], a[0] = 0: the inner rows themselves):
+//   Tail.sequence.3, Tail.identity.0     rows with margin <= a[l]
+//   Tail.sequence.0                      <= a[l] + 1   (sequence.3 is submanifold)
+//   Decode.sequence.0 (level-l outputs)  <= a[l] + 2   (sequence.0 is submanifold and reads cat(skip, decoded))
+//   Tail.sequence.3 one level down       <= a[l + 1] = ceil((a[l] + 2) / 2)   (Decode is the inverse convolution)
+// -> a = 0, 1, 2, 2, 2, ...  The encoder side (Head, Encode) has a receptive field wider than any halo and runs in full.
+#define ST_RULE_NEED_CLASSES 3  // margin <= a[l], = a[l] + 1, = a[l] + 2: the three launch prefixes of a level's need list
+__host__ __device__ inline int st_rule_need_base(int level) {
+    int a = 0;
+    for (int l = 0; l < level; l++) a = (a + 2 + 1) >> 1;
+    return a;
+}
+// the level-`level` box of a level-0 box side [lo, hi]
+__host__ __device__ inline void st_rule_need_box(int lo, int hi, int level, int* blo, int* bhi) {
+    *blo = lo >> level;                       // `level` floor-halvings
+    *bhi = (hi + (1 << level) - 1) >> level;  // `level` times (hi + 1) >> 1
+}
+// margin class of a row at level `level`: 0 .. ST_RULE_NEED_CLASSES - 1, or ST_RULE_NEED_CLASSES = no convolution of the decoder needs it.
+// lo / hi: the block's level-0 box (lo > hi: the block has none).
+__host__ __device__ inline int st_rule_need_class(const int c[3], const int lo[3], const int hi[3], int level) {
+    int m = 0;
+    for (int a = 0; a < 3; a++) {
+        if (lo[a] > hi[a]) return ST_RULE_NEED_CLASSES;
+        int blo, bhi;
+        st_rule_need_box(lo[a], hi[a], level, &blo, &bhi);
+        const int d = c[a] < blo ? blo - c[a] : (c[a] > bhi ? c[a] - bhi : 0);
+        m = d > m ? d : m;
+    }
+    const int over = m - st_rule_need_base(level);
+    return over <= 0 ? 0 : (over < ST_RULE_NEED_CLASSES ? over : ST_RULE_NEED_CLASSES);
+}
+
 // Per-cloud extent.  A cloud's coarse sets are clipped at its OWN extent, so they do not depend on what else is in the batch:
 // ext[seg * 3 + axis] = largest coordinate.  A workgroup reduces into m (LDS, nseg * 3 words), then one atomicMax per word.
 __device__ __forceinline__ void st_ext_clear(int* m, int nseg) {

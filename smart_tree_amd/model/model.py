@@ -146,21 +146,33 @@ class Smart_Tree:
         return torch.cat(blocks).float().contiguous()
 
     # -- building blocks ---------------------------------------------------------------------
-    def _conv(self, name, x, nbr, n_out, x1=None, bn=None, residual=None, relu=False, row_order=None):
+    def _conv(self, name, x, nbr, n_out, x1=None, bn=None, residual=None, relu=False, row_order=None, rows=None):
+        """rows (optional): (list, parity) -- compute only the listed rows of the n_out the level has (sparse_ops.sparse_conv
+        `level_rows`); a list that keeps more than LIST_MAX_SHARE of the level is not worth its gather: the layer runs as without one."""
         a = self.bn[bn] if bn else None
         out_half = self.fp16 and self.w[name].shape[2] % 16 == 0  # half storage on the levels with >= 16 channels
+        listed = {}
+        if rows is not None and rows[0].shape[0] <= self.LIST_MAX_SHARE * n_out:
+            listed = dict(level_rows=n_out, parity=rows[1])
+            row_order, n_out = rows[0], rows[0].shape[0]
         return ops.sparse_conv(x, self.w[name], nbr, n_out, x1=x1, scale=a.scale if a else None,
                                shift=a.shift if a else None, residual=residual, relu=relu,
                                wp=self.wp.get(name) if self.use_mfma else None, out_half=out_half,
                                wp16=self.wp16.get(name), row_order=row_order,
-                               wq=self.wq.get(name) if self.use_mfma and self.use_b3 and not self.fp16 else None)
+                               wq=self.wq.get(name) if self.use_mfma and self.use_b3 and not self.fp16 else None, **listed)
 
-    def _res_block(self, prefix, x, nbr, x1=None):
-        """ResBlock.forward (model_blocks.py:149-156); x1 != None is the Tail on cat(skip, decoded)."""
+    LIST_MAX_SHARE = 0.95
+
+    def _res_block(self, prefix, x, nbr, x1=None, need=None):
+        """ResBlock.forward (model_blocks.py:149-156); x1 != None is the Tail on cat(skip, decoded).
+        need (the Tail of a level with row lists): sequence.3 and the identity compute the rows with margin <= a[l], sequence.0 one
+        voxel further out (csrc/st_rule.h)."""
         n = x.shape[0]
-        h = self._conv(prefix + ".sequence.0", x, nbr, n, x1=x1, bn=prefix + ".sequence.1", relu=True)
-        ident = self._conv(prefix + ".identity.0", x, None, n, x1=x1) if x1 is not None else x
-        return self._conv(prefix + ".sequence.3", h, nbr, n, bn=prefix + ".sequence.4", residual=ident, relu=True)
+        r0 = (need.order[: need.counts[0]], False) if need is not None else None
+        r1 = (need.order[: need.counts[1]], False) if need is not None else None
+        h = self._conv(prefix + ".sequence.0", x, nbr, n, x1=x1, bn=prefix + ".sequence.1", relu=True, rows=r1)
+        ident = self._conv(prefix + ".identity.0", x, None, n, x1=x1, rows=r0) if x1 is not None else x
+        return self._conv(prefix + ".sequence.3", h, nbr, n, bn=prefix + ".sequence.4", residual=ident, relu=True, rows=r0)
 
     def _ublock(self, prefix, x, pyr, level):
         """UBlock.forward (model_blocks.py:224-243)."""
@@ -173,10 +185,12 @@ class Smart_Tree:
                        relu=True)
         self._record(f"enc{level}", z)
         z = self._ublock(prefix + ".U", z, pyr, level + 1)
+        need = pyr.need[level] if pyr.need else None
         d = self._conv(prefix + ".Decode.sequence.0", z, pyr.up[level], n_fine, bn=prefix + ".Decode.sequence.1",
-                       relu=True, row_order=pyr.up_order[level] if pyr.up_order else None)
+                       relu=True, row_order=pyr.up_order[level] if pyr.up_order else None,
+                       rows=(need.up_order, True) if need is not None else None)  # the rows with margin <= a[l] + 2
         self._record(f"dec{level}", d)
-        x = self._res_block(prefix + ".Tail", x, pyr.subm[level], x1=d)
+        x = self._res_block(prefix + ".Tail", x, pyr.subm[level], x1=d, need=need)
         self._record(f"tail{level}", x)
         return x
 
@@ -184,17 +198,26 @@ class Smart_Tree:
         if self.trace is not None:
             self.trace[name] = x
 
-    def features(self, sparse_input):
+    def features(self, sparse_input, inner_mask=None):
         """input conv + UNet -> [N, planes[0]] features of the finest level, rows in the input's order.
         Internally the voxels are processed in a spatially coherent order (`spatial_order`, on by default): every output row
         is computed on its own from the rows its neighbour table names, so the values do not depend on the row order, but
-        gathers hit rows that are close in memory and the 16 rows of a matrix-core tile share their live offsets."""
+        gathers hit rows that are close in memory and the 16 rows of a matrix-core tile share their live offsets.
+        inner_mask ([N] uint8 / bool, optional): the caller keeps the rows with inner_mask != 0 only.  With brick rulebooks the
+        decoder then computes just the rows those depend on (csrc/st_rule.h): the kept rows come out bit for bit as without the
+        mask, the others are zero or features of rows that happened to be needed.  Ignored with hash-table rulebooks or a trace."""
+        return self._features(sparse_input, inner_mask)[0]
+
+    def _features(self, sparse_input, inner_mask=None):
+        """features() and the mask of the rows the heads evaluate (uint8), or None for every row."""
         coords = sparse_input.indices.contiguous()
         feats = sparse_input.features.contiguous().float()
         blk_seg, n_seg = getattr(sparse_input, "blk_seg", None), getattr(sparse_input, "n_seg", 1)
         reorder = self.spatial_order and self.trace is None and coords.shape[0] > 1
         hint = getattr(sparse_input, "brick_hint", None)
-        bricks = ops.brick_pyramid(coords, self.depth, hint[0], hint[1], blk_seg, n_seg) if reorder and hint and self.use_bricks else None
+        if self.generic_heads:  # (heads as pointwise convolutions have no list form)
+            inner_mask = None
+        bricks = ops.brick_pyramid(coords, self.depth, hint[0], hint[1], blk_seg, n_seg, inner_mask) if reorder and hint and self.use_bricks else None
         if bricks is not None:  # occupancy bricks: the order and every table from one call, no hash probes, one read-back
             pyr, order = bricks
             feats = ops.move_rows(feats, order)
@@ -210,18 +233,28 @@ class Smart_Tree:
             x = self._conv("input_conv.sequence.0", feats, None, feats.shape[0], bn="input_conv.sequence.1", relu=True)
             self._record("input", x)
             x = self._ublock("UNet", x, pyr, 0)
-        if order is not None:
+        keep = None
+        if bricks is not None and pyr.need and x.element_size() == 4 and pyr.need[0].counts[0] <= self.LIST_MAX_SHARE * x.shape[0]:
+            # only the rows with margin 0 leave the network: they are moved back, and the heads evaluate the inner rows among them
+            keep = inner_mask.contiguous().view(torch.uint8)
+            x = ops.move_rows(x, order, scatter=True, rows=pyr.need[0].order[: pyr.need[0].counts[0]])
+        elif order is not None:
             x = ops.move_rows(x, order, scatter=True)
-        return x
+        return x, keep
 
-    def forward(self, sparse_input) -> Dict[str, torch.Tensor]:
-        x = self.features(sparse_input)
-        radius, direction, class_l, _, _ = self._generic_heads(x, False) if self.generic_heads else ops.mlp_heads(x, self.head_params)
+    def _heads(self, x, keep, with_tail):
+        if self.generic_heads:
+            return self._generic_heads(x, with_tail)
+        return ops.mlp_heads(x, self.head_params, with_tail=with_tail, keep=keep)
+
+    def forward(self, sparse_input, inner_mask=None) -> Dict[str, torch.Tensor]:
+        """inner_mask: see features(); the outputs of the rows it keeps are bit for bit those of forward(sparse_input), the other
+        rows' are zero (or, where nothing could be left out, computed as without the mask)."""
+        radius, direction, class_l, _, _ = self._heads(*self._features(sparse_input, inner_mask), False)
         return {"radius": radius, "direction": direction, "class_l": class_l}
 
     __call__ = forward
 
-    def forward_fused_tail(self, sparse_input):
+    def forward_fused_tail(self, sparse_input, inner_mask=None):
         """forward() plus ModelInference's exp(radius)*direction and argmax in the same kernel."""
-        x = self.features(sparse_input)
-        return self._generic_heads(x, True) if self.generic_heads else ops.mlp_heads(x, self.head_params, with_tail=True)
+        return self._heads(*self._features(sparse_input, inner_mask), True)

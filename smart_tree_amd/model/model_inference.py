@@ -46,16 +46,20 @@ def load_model(model_path, weights_path, device=torch.device("cuda:0"), fp16: bo
 class ModelInference:
     def __init__(self, model_path, weights_path, voxel_size: float, block_size: float, buffer_size: float,
                  num_workers=8, batch_size=4, device=torch.device("cuda:0"), verbose=False, fp16: bool = False,
-                 blocking: str = "blocks"):
+                 blocking: str = "blocks", prune_halo: bool = True):
         """blocking (additive keyword): "blocks" = the reference's scheme (4 m cubes + halo, every block on its
         own voxel grid, halo voxels evaluated and thrown away: ~1.5x the voxels); "whole" = OPT-IN approximate mode: the cloud
         is voxelised once on one grid anchored at its own bounding box (st_voxelize_cloud_seg) and the network sees every
         voxel exactly once with its true neighbourhood.  NOT result-preserving: the reference's grids are anchored per block
         (dataset.py:196-212) and its halo (0.4 m) is shorter than the network's receptive field, so the per-block outputs
-        are themselves an approximation of this mode's (tests/test_whole_cloud_mode.py quantifies the difference)."""
+        are themselves an approximation of this mode's (tests/test_whole_cloud_mode.py quantifies the difference).
+        prune_halo (additive keyword): in blocks mode with `return_masked`, the halo voxels are still evaluated by the encoder
+        but the decoder computes only the rows the inner voxels depend on (Smart_Tree.features `inner_mask`): the masked rows
+        are bit for bit what they are without it, the medial vector and class of the halo rows -- which the mask drops -- are zero."""
         if blocking not in ("blocks", "whole"):
             raise ValueError(f"ModelInference: blocking must be 'blocks' or 'whole', got {blocking!r}")
         self.blocking = blocking
+        self.prune_halo = bool(prune_halo)
         self.device = torch.device(device)
         self.verbose = verbose
         self.voxel_size = voxel_size
@@ -96,7 +100,8 @@ class ModelInference:
         # radius / direction / class_l come out exactly as model.forward(sparse_input) gives them;
         # exp(radius)*direction and argmax (reference :87-88) are fused into the head kernel
         with profiling.stage("unet"):
-            _, _, _, mv, cls = self.model.forward_fused_tail(sparse_input)
+            prune = self.prune_halo and return_masked and self.blocking == "blocks"
+            _, _, _, mv, cls = self.model.forward_fused_tail(sparse_input, vb.mask if prune else None)
         masks = vb.mask
         self.last_point_index = vb.point_index
         lc = Cloud(xyz=sparse_input.features, rgb=vb.feats[:, 3:6].contiguous(), medial_vector=mv, class_l=cls,

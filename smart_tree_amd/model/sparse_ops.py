@@ -85,6 +85,14 @@ def build_strided_rulebook(coords: torch.Tensor, h: CoordHash, blk_seg: Optional
 
 
 @dataclass
+class NeedLists:
+    """The rows of one level the decoder has to compute when only the inner voxels' outputs are kept (csrc/st_rule.h)."""
+    order: torch.Tensor  # [counts[2]] int32: the rows with margin <= a[l], then = a[l] + 1, then = a[l] + 2 (brick order inside each)
+    counts: tuple  # the three prefix lengths: a convolution with threshold a[l] + t launches over order[: counts[t]]
+    up_order: torch.Tensor  # the entries of the tagged parity order whose row has margin <= a[l] + 2
+
+
+@dataclass
 class RulebookPyramid:
     """Per-level active sets and neighbour tables of one batch; built once, shared by all convs."""
     coords: List[torch.Tensor] = field(default_factory=list)
@@ -92,6 +100,7 @@ class RulebookPyramid:
     down: List[torch.Tensor] = field(default_factory=list)  # down[l]: level l -> l+1
     up: List[torch.Tensor] = field(default_factory=list)  # up[l]:   level l+1 -> l
     up_order: List[torch.Tensor] = field(default_factory=list)  # up_order[l]: launch order of level l's rows for up[l]
+    need: List[NeedLists] = field(default_factory=list)  # need[l], l < depth: only from brick_pyramid with an inner mask
 
 
 def build_pyramid(coords: torch.Tensor, depth: int, blk_seg: Optional[torch.Tensor] = None, n_seg: int = 1) -> RulebookPyramid:
@@ -111,11 +120,13 @@ def build_pyramid(coords: torch.Tensor, depth: int, blk_seg: Optional[torch.Tens
 
 
 def brick_pyramid(coords: torch.Tensor, depth: int, n_blocks: int, coord_bound: int, blk_seg: Optional[torch.Tensor] = None,
-                  n_seg: int = 1):
+                  n_seg: int = 1, inner_mask: Optional[torch.Tensor] = None):
     """The whole pyramid from occupancy bricks + popcount ranks (csrc/brick.hip): no hash probes, no sorts, ONE read-back.
     Returns (RulebookPyramid, order0) or None when the structure cannot be sized for (n_blocks, coord_bound) -- the caller
     then takes `build_pyramid`.  Level 0's rows are the input voxels in brick order (row p = input voxel order0[p]); the
-    tables are views with row stride = the level's capacity (`sparse_conv` passes the stride on)."""
+    tables are views with row stride = the level's capacity (`sparse_conv` passes the stride on).
+    inner_mask ([n0] uint8 / bool, input order; optional): the voxels whose outputs are kept -> `pyr.need[l]` for every l < depth,
+    the row lists the decoder's convolutions launch over (st_brick_pyramid_need; their lengths ride on the same read-back)."""
     L = _lib.lib()
     dev = coords.device
     n0 = coords.shape[0]
@@ -124,6 +135,10 @@ def brick_pyramid(coords: torch.Tensor, depth: int, n_blocks: int, coord_bound: 
     if blk_seg is None or blk_seg.numel() == 0:
         n_seg = 1
     i32 = dict(dtype=torch.int32, device=dev)
+    if inner_mask is not None:
+        if inner_mask.shape != (n0,) or inner_mask.element_size() != 1:
+            raise ValueError("brick_pyramid: inner_mask must be [n0] uint8 / bool")
+        inner_mask = inner_mask.contiguous().view(torch.uint8)
     for attempt in range(2):
         # k3 s2 p1: a surface-like set shrinks to ~half per level.  Isolated voxels reach up to 8 outputs each and thin lines
         # ~1.1 per fine voxel: the retry sizes every level for 8x the level below, clamped by what the declared geometry can
@@ -149,13 +164,17 @@ def brick_pyramid(coords: torch.Tensor, depth: int, n_blocks: int, coord_bound: 
             down = [torch.empty((27, caps[l + 1]), **i32) for l in range(depth)]
             up = [torch.empty((27, caps[l]), **i32) for l in range(depth)]
             up_order = [torch.empty(caps[l] + 16, **i32) for l in range(depth)]
+            need_order = [torch.empty(caps[l], **i32) for l in range(depth)] if inner_mask is not None else []
+            up_need = [torch.empty(caps[l], **i32) for l in range(depth)] if inner_mask is not None else []
         except torch.OutOfMemoryError:
             return None
         arr = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
         counts = (ctypes.c_int64 * (depth + 1))()
-        rc = L.st_brick_pyramid(_lib.ptr(coords), n0, int(n_blocks), int(coord_bound), depth, _lib.ptr(blk_seg) if n_seg > 1 else None,
-                                n_seg, c_caps, _lib.ptr(order0), arr(coords_out), arr(subm), arr(down), arr(up), arr(up_order), counts,
-                                _lib.ptr(ws), ws.numel(), _lib.stream(dev))
+        need_counts = (ctypes.c_int64 * max(4 * depth, 1))()
+        rc = L.st_brick_pyramid_need(_lib.ptr(coords), n0, int(n_blocks), int(coord_bound), depth, _lib.ptr(blk_seg) if n_seg > 1 else None,
+                                     n_seg, c_caps, _lib.ptr(order0), arr(coords_out), arr(subm), arr(down), arr(up), arr(up_order), counts,
+                                     _lib.ptr(inner_mask), arr(need_order), arr(up_need), need_counts, _lib.ptr(ws), ws.numel(),
+                                     _lib.stream(dev))
         if rc == 0:
             break
         if b"outside the declared bounds" in L.st_last_error():
@@ -164,7 +183,7 @@ def brick_pyramid(coords: torch.Tensor, depth: int, n_blocks: int, coord_bound: 
             _lib.check(rc)
         if attempt == 1:
             return None  # still over capacity: hash-table builders
-        del ws, order0, coords_out, subm, down, up, up_order
+        del ws, order0, coords_out, subm, down, up, up_order, need_order, up_need
     n = [int(counts[l]) for l in range(depth + 1)]
     pyr = RulebookPyramid()
     for l in range(depth + 1):
@@ -174,6 +193,9 @@ def brick_pyramid(coords: torch.Tensor, depth: int, n_blocks: int, coord_bound: 
             pyr.down.append(down[l][:, : n[l + 1]])
             pyr.up.append(up[l][:, : n[l]])
             pyr.up_order.append(up_order[l][: n[l]])
+            if inner_mask is not None:
+                c = tuple(int(need_counts[4 * l + t]) for t in range(4))
+                pyr.need.append(NeedLists(need_order[l][: c[2]], c[:3], up_need[l][: c[3]]))
     return pyr, order0
 
 
@@ -203,12 +225,20 @@ def spatial_order(coords: torch.Tensor) -> torch.Tensor:
     return order
 
 
-def move_rows(x: torch.Tensor, order: torch.Tensor, scatter: bool = False) -> torch.Tensor:
+def move_rows(x: torch.Tensor, order: torch.Tensor, scatter: bool = False, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x[order] (gather) or the inverse (out[order] = x, scatter) for a [N, C] tensor, order int32 [N]: 4-byte elements through
-    st_move_rows, 2-byte elements (any C) through st_move_rows_h."""
+    st_move_rows, 2-byte elements (any C) through st_move_rows_h.
+    rows (optional, int32; 4-byte elements only): only the positions p in `rows` are moved, the other rows of the result are zero."""
     L = _lib.lib()
     x = x.contiguous()
     assert x.element_size() in (4, 2) and x.ndim == 2 and order.dtype == torch.int32
+    if rows is not None:
+        assert x.element_size() == 4 and rows.dtype == torch.int32
+        out = torch.zeros_like(x)
+        if rows.numel():
+            _lib.check(L.st_move_rows_list(_lib.ptr(x), x.shape[1], _lib.ptr(order), _lib.ptr(rows), rows.numel(), _lib.ptr(out), int(scatter),
+                                           _lib.stream(x.device)))
+        return out
     out = torch.empty_like(x)
     move = L.st_move_rows if x.element_size() == 4 else L.st_move_rows_h
     if x.element_size() == 4 or x.shape[1]:
@@ -315,67 +345,95 @@ def sparse_conv(x0: torch.Tensor, w: torch.Tensor, nbr: Optional[torch.Tensor], 
                 shift: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
                 relu: bool = False, wp: Optional[torch.Tensor] = None, out_half: bool = False,
                 wp16: Optional[torch.Tensor] = None, row_order: Optional[torch.Tensor] = None,
-                wq: Optional[torch.Tensor] = None) -> torch.Tensor:
+                wq: Optional[torch.Tensor] = None, level_rows: Optional[int] = None, parity: Optional[bool] = None) -> torch.Tensor:
     """y = act(bn(sum_k W_k . cat(x0, x1)[nbr[k]]) + residual); w is [K, Cin, Cout].
     wp (optional): the same weights in MFMA order -> the matrix-core kernel is used.
     wq (optional, b3_weight(w)): the weights as three bf16 planes -> the split-bf16 matrix-core kernel (float32 accuracy on the
     bf16 pipe) where the shape is eligible (b3_eligible); takes precedence over wp.
     row_order (optional, [n_out] int32): launch order of the output rows (never changes the result).
+    level_rows (optional): row_order is a LIST of n_out of the level's level_rows rows -- only those are computed, the result has
+    level_rows rows and the others are not written (POISON_OUTPUTS: NaN).  parity says whether the list stands for the layer's
+    tagged parity order (default: any row_order does).  The kernel instance and row-tile variant are chosen from level_rows and
+    parity, never from the list, so a row gets the same bits from a list launch as from a launch of the whole level.
     Half-precision storage mode: a float16 x0 and / or out_half select st_sparse_conv_f16_fwd (wp16 = mfma_weight16_half(w): the layout depends on Cin / Cout, see include/smarttree_hip.h)."""
     L = _lib.lib()
     K, cin, cout = w.shape
     c0 = x0.shape[1]
     nbr_ptr, nbr_stride = _nbr_args(nbr)
-    if n_out == 0:  # an empty active set (a cloud without a block of > 20 points): nothing to launch
-        return torch.empty((0, cout), dtype=torch.float16 if out_half else torch.float32, device=x0.device)
+    listed = level_rows is not None
+    if listed and row_order is None:
+        raise ValueError("sparse_conv: level_rows needs the list of rows (row_order)")
+    n_rows = int(level_rows) if listed else n_out
+    if parity is None:
+        parity = row_order is not None
+    if n_out == 0:  # an empty active set (a cloud without a block of > 20 points) or an empty list: nothing to launch
+        return _conv_output(n_rows, cout, out_half, x0.device)
     in_half = x0.dtype == torch.float16
     # 16 -> 16 submanifold convs run on the vector kernel (lane = voxel, weights from scalar registers): with Morton-ordered
     # rows it beats the matrix-core kernel wherever the level fills the chip (67 % against 53 % of the HBM peak at 1.5M rows,
     # profiles/r02_conv_layers_batch16.txt).  At EVERY size, not only the large ones: the two kernels round differently in
     # the last bit (the matrix core does not evaluate a k-ordered fmaf chain exactly), and a cloud must get the same values
     # alone and inside a batch (tests/test_batch.py).
-    big_16 = cin == 16 and cout == 16 and nbr is not None and row_order is None and x1 is None
+    big_16 = cin == 16 and cout == 16 and nbr is not None and not parity and x1 is None
     # per branch: entry point, its weights, profiling name, arguments between y and row_order, arguments after nbr_stride
     mid, tail = (), ()
     if in_half or out_half:
         both = in_half and out_half
         if both and wp16 is None:
             raise ValueError("half -> half convolution needs the half-precision MFMA weights (wp16)")
-        entry, wt, mid = L.st_sparse_conv_f16_fwd, (wp16 if both else w), (int(in_half), int(out_half))
+        entry, wt, mid = "st_sparse_conv_f16_fwd", (wp16 if both else w), (int(in_half), int(out_half))
         name = f"k_sparse_conv_mfma_f16x<{cin},{cout}>" if both else f"k_sparse_conv<{cin},{cout}> {'h->f' if in_half else 'f->h'}"
     elif wq is not None and b3_eligible(cin, cout, c0):
-        entry, wt, name, tail = L.st_sparse_conv_b3_fwd, wq, f"k_sparse_conv_mfma_b3<{cin},{cout}>", (int(B3_VARIANT),)
+        entry, wt, name, tail = "st_sparse_conv_b3_fwd", wq, f"k_sparse_conv_mfma_b3<{cin},{cout}>", (int(B3_VARIANT),)
     elif wp is not None and mfma_eligible(cin, cout, c0) and not big_16:
-        entry, wt, name, tail = L.st_sparse_conv_mfma_fwd, wp, f"k_sparse_conv_mfma<{cin},{cout}>", (int(MFMA_VARIANT),)
+        entry, wt, name, tail = "st_sparse_conv_mfma_fwd", wp, f"k_sparse_conv_mfma<{cin},{cout}>", (int(MFMA_VARIANT),)
     else:
-        entry, wt, name = L.st_sparse_conv_fwd, w, f"k_sparse_conv<{cin},{cout}>"
+        entry, wt, name = "st_sparse_conv_fwd", w, f"k_sparse_conv<{cin},{cout}>"
+    if listed and entry != "st_sparse_conv_fwd":  # (the vector kernels have one instance per shape at every size: the list is their row_order)
+        entry, tail = entry.replace("_fwd", "_list_fwd"), tail + (n_rows, int(parity))
+    entry = getattr(L, entry)
     esz_in, esz_out = (2 if in_half else 4), (2 if out_half else 4)
-    y = torch.empty((n_out, cout), dtype=torch.float16 if out_half else torch.float32, device=x0.device)
+    y = _conv_output(n_rows, cout, out_half, x0.device)
+    rows = row_order[:n_out] if listed else None  # profiling: the pairs of the computed rows only
     # algorithmic bytes (SURVEY.md 8d): P*(Cin*4 + 4) + N*Cout*4 (pointwise: N*(Cin+Cout)*4; 2-byte elements on a half side); the
     # pair count is evaluated lazily, after the timed region
-    nbytes = (lambda: (_pair_count(nbr) if nbr is not None else n_out) * (cin * esz_in + (4 if nbr is not None else 0))
+    nbytes = (lambda: (_pair_count(nbr, rows) if nbr is not None else n_out) * (cin * esz_in + (4 if nbr is not None else 0))
               + n_out * cout * esz_out) if profiling.enabled() else 0
-    nflops = (lambda: 2.0 * (_pair_count(nbr) if nbr is not None else n_out) * cin * cout) if profiling.enabled() else 0
+    nflops = (lambda: 2.0 * (_pair_count(nbr, rows) if nbr is not None else n_out) * cin * cout) if profiling.enabled() else 0
     with profiling.kernel(name + ("" if nbr is not None else " k1"), nbytes, nflops):
         _lib.check(entry(_lib.ptr(x0), c0, _lib.ptr(x1), cin, nbr_ptr, K, n_out, _lib.ptr(wt), cout, _lib.ptr(scale), _lib.ptr(shift),
                          _lib.ptr(residual), int(relu), _lib.ptr(y), *mid, _lib.ptr(row_order), _lib.stream(x0.device), nbr_stride, *tail))
     return y
 
 
+POISON_OUTPUTS = False  # test hook: convolution outputs start as NaN instead of uninitialised memory (a read of a row that a list launch left out shows)
+
+
+def _conv_output(n_rows: int, cout: int, out_half: bool, device) -> torch.Tensor:
+    dtype = torch.float16 if out_half else torch.float32
+    if POISON_OUTPUTS:
+        return torch.full((n_rows, cout), float("nan"), dtype=dtype, device=device)
+    return torch.empty((n_rows, cout), dtype=dtype, device=device)
+
+
 _pairs_cache = {}
 
 
-def _pair_count(nbr: torch.Tensor) -> int:
-    """Active (input, output) pairs of a neighbour table (profiling only; cached per table)."""
-    key = (id(nbr), profiling.generation())  # the thunk keeps the tensor alive, so the id is stable within one collection
+def _pair_count(nbr: torch.Tensor, rows: Optional[torch.Tensor] = None) -> int:
+    """Active (input, output) pairs of a neighbour table, or of its columns `rows` (entries of a row list, tags allowed) when a
+    convolution computes only those (profiling only; cached per table and list)."""
+    key = (id(nbr), id(rows), profiling.generation())  # the thunk keeps the tensors alive, so the ids are stable within one collection
     if key not in _pairs_cache:
         if len(_pairs_cache) > 4096:
             _pairs_cache.clear()
-        _pairs_cache[key] = int((nbr >= 0).sum().item())
+        cols = nbr if rows is None else nbr[:, (rows & 0x0FFFFFFF).long()]
+        _pairs_cache[key] = int((cols >= 0).sum().item())
     return _pairs_cache[key]
 
 
-def mlp_heads(x: torch.Tensor, params: torch.Tensor, with_tail: bool = False):
+def mlp_heads(x: torch.Tensor, params: torch.Tensor, with_tail: bool = False, keep: Optional[torch.Tensor] = None):
+    """The three heads (+ ModelInference's tail) of every row of x; keep ([n] uint8, optional): of the rows with keep != 0 only --
+    the others are not read (they may never have been computed) and are zero in every output."""
     L = _lib.lib()
     n, dev = x.shape[0], x.device
     radius = torch.empty((n, 1), dtype=torch.float32, device=dev)
@@ -385,6 +443,6 @@ def mlp_heads(x: torch.Tensor, params: torch.Tensor, with_tail: bool = False):
     cls = torch.empty((n, 1), dtype=torch.int64, device=dev) if with_tail else None
     if n == 0:
         return radius, direction, class_l, mv, cls
-    _lib.check(L.st_pointwise_mlp_heads(_lib.ptr(x), n, _lib.ptr(params), _lib.ptr(radius), _lib.ptr(direction),
-                                        _lib.ptr(class_l), _lib.ptr(mv), _lib.ptr(cls), _lib.stream(dev)))
+    _lib.check(L.st_pointwise_mlp_heads_keep(_lib.ptr(x), n, _lib.ptr(keep), _lib.ptr(params), _lib.ptr(radius), _lib.ptr(direction),
+                                             _lib.ptr(class_l), _lib.ptr(mv), _lib.ptr(cls), _lib.stream(dev)))
     return radius, direction, class_l, mv, cls

@@ -36,7 +36,8 @@ extern "C" {
  * 110: st_bridge_components_seg and its size query added (no existing signature changed).
  * 111: st_segment_points_seg and its size query added (no existing signature changed).
  * 112: st_brick_pyramid_need, the st_sparse_conv_{mfma,b3,f16}_list_fwd calls, st_pointwise_mlp_heads_keep and st_move_rows_list
- * added; st_abi_entries(3) added (no existing signature or st_abi_entries value changed). */
+ * added; st_abi_entries(3) added (no existing signature or st_abi_entries value changed).
+ * 113: st_fit_tubes and its size query added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -605,6 +606,32 @@ int st_segment_points_seg(const float* pts, int64_t n, const int32_t* pt_seg_off
                           const float* r2, int64_t m, const int32_t* tube_seg_off, int nseg, float max_distance, int form,
                           int32_t* tube, float* residual, float* vec, float* rad, int64_t* tally, void* ws, int64_t ws_bytes,
                           void* stream);
+
+/* ---- fitting: every tube to the points segmented onto it (csrc/fit.hip) -------------------------------------------------
+ * replaces: nothing -- the reference's radii are the network's prediction, corrected by the box filter of `smooth` only.
+ *
+ * pts [n,3]; tube [n] int32 as st_segment_points_seg wrote it (a position in the tube arrays; -1 or any value outside [0, m):
+ * the point takes no part); a, b [m,3], r1, r2 [m].  Per tube, float32, no contraction:
+ *   frame: ab = b - a; k = the coordinate with the smallest |ab_k| (ties to the lowest); e1 = normalise(cross(ab, unit_k)),
+ *   e2 = normalise(cross(ab, e1)), normalise(x) = x / sqrtf(dot(x, x)), dot = (x*x' + y*y') + z*z'.
+ *   a point enters when it is finite, q = dot(p - a, ab) / dot(ab, ab) satisfies 0 <= q <= 1 (never for a zero-length tube; a point
+ *   past an end cap is left out), rho = the distance to the axis at q is > 0, and max_relative < 0 or
+ *   |rho - r(q)| <= max_relative * r(q) with r(q) = (1 - q)*r1 + q*r2.
+ *   it adds, with w the unit vector from the axis to the point, c = dot(w, e1), s = dot(w, e2): moments [10*m] int64 (optional),
+ *   per tube the count and the sums of llrintf(x * 2^24), the scaled value clamped to +-2^40, of c*c, c*s, s*s, c, s, rho*c, rho*s,
+ *   rho, rho*rho: integer sums, bit-identical from run to run.
+ * The solve (float64, from the integer moments): one Gauss-Newton step of the geometric circle fit, the least squares of
+ * rho_i - (c_i, s_i).(cu, cv) - R = 0.  spread = the smaller eigenvalue of the covariance of (c, s).
+ * fit [8*m] float64 (optional), per tube: N, R, the offset cu*e1 + cv*e2 (3), the rms of the linear residual, the spread, the status:
+ *   0 not fitted (N < min_points; the rest of the row is 0), 1 radius only (spread < min_spread: R = the mean of rho, offset 0),
+ *   2 full fit.
+ * Enqueue-only.  n = 0 or m = 0 launches no kernel and zeroes the outputs.  Refused, nothing launched: n or m outside [0, 2^31),
+ * a NaN max_relative or min_spread, a missing input array (-1); a workspace below st_fit_tubes_workspace_bytes(n, m) (-2; the size
+ * query returns -1 for sizes the call refuses). */
+int64_t st_fit_tubes_workspace_bytes(int64_t n, int64_t m);
+int st_fit_tubes(const float* pts, int64_t n, const int32_t* tube, const float* a, const float* b, const float* r1, const float* r2,
+                 int64_t m, float max_relative, int64_t min_points, double min_spread, int64_t* moments, double* fit, void* ws,
+                 int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,9 @@ set and `view_path` given, the views are rendered offscreen (smart_tree_amd/rend
 dependency-free files (util/file.py).  Additive: `segment_cloud=True` assigns every point of the preprocessed cloud to
 a tree and a branch of the post-processed skeleton (segmentation.py) and keeps the result in `last_segmentation`;
 `save_outputs` then also writes `segmentation.npz` / `seg_cld.ply`, `view_skeletons` also `segmentation.png`.
+Additive: `refine_skeletons=True` fits the post-processed skeleton's radii and axes to the points the network called wood
+(refine.py); the refined skeleton is what is returned, segmented, drawn and saved, `last_raw_skeleton` / `last_fit` keep the
+skeleton as it was and the per-tube report, and `save_outputs` also writes `skeleton_fit.npz`.
 """
 from __future__ import annotations
 
@@ -28,7 +31,7 @@ class Pipeline:
                  smooth_kernel_size=0, prune_skeletons=False, min_skeleton_radius=0.0, min_skeleton_length=1000,
                  view_model_output=False, view_skeletons=False, save_outputs=False, save_path="/", branch_classes=[0],
                  cmap=[[1, 0, 0], [0, 1, 0]], device=torch.device("cuda:0"), view_path=None, segment_cloud=False,
-                 segment_max_distance=None):
+                 segment_max_distance=None, refine_skeletons=False, refine_iterations=2, refine_max_relative=0.5):
         self.preprocessing = preprocessing
         self.model_inference = model_inference
         self.skeletonizer = skeletonizer
@@ -51,6 +54,11 @@ class Pipeline:
         self.segment_max_distance = segment_max_distance
         self.last_segmentation = None
         self._segmented = None  # (cloud, its segmentation) the next write_views call draws
+        self.refine_skeletons = refine_skeletons
+        self.refine_iterations = refine_iterations
+        self.refine_max_relative = refine_max_relative
+        self.last_raw_skeleton = None
+        self.last_fit = None
 
     def process_cloud(self, path: Path = None, cloud: Cloud = None) -> DisjointTreeSkeleton:
         cloud = load_cloud(path) if path is not None else cloud
@@ -65,6 +73,8 @@ class Pipeline:
         with profiling.stage("post_process"):
             self.post_process(skeleton)
             skeleton.skeletons  # materialise: device post-processing kernel, one D->H copy, BranchSkeleton objects
+        if self.refine_skeletons:
+            skeleton = self._refine(branch_cloud, skeleton)
         if self.segment_cloud:
             self._segment(cloud, skeleton)
             self._segmented = (cloud, self.last_segmentation)
@@ -85,7 +95,19 @@ class Pipeline:
             if self.segment_cloud:  # the reference's fourth file name (pipeline.py:93 `seg_cld.ply`), here the points by branch
                 from .segmentation import save_segmentation
                 save_segmentation(sp, cloud, self.last_segmentation)
+            if self.refine_skeletons:
+                self.last_fit.save(sp / "skeleton_fit.npz")
         return skeleton
+
+    def _refine(self, branch_cloud: Cloud, skeleton):
+        """The skeleton (or the skeletons of a batch) fitted to the points it was made from: the points of `branch_classes`."""
+        from .refine import refine_skeleton
+
+        with profiling.stage("refine_skeleton"):
+            self.last_raw_skeleton = skeleton
+            refined, self.last_fit = refine_skeleton(branch_cloud, skeleton, iterations=self.refine_iterations,
+                                                     max_relative=self.refine_max_relative, device=self.device)
+        return refined
 
     def _segment(self, cloud: Cloud, skeleton) -> None:
         """Every point the caller gave, in the skeleton's frame (the cloud `preprocessing` returned), to its tree and branch."""
@@ -118,6 +140,8 @@ class Pipeline:
             parts = skeleton.split()  # device post-processing of all clouds, ONE device-to-host copy, per-cloud views
         if len(parts) != len(clouds):
             raise RuntimeError(f"process_clouds: {len(parts)} skeleton(s) for a batch of {len(clouds)} clouds")
+        if self.refine_skeletons:  # one segmentation and one fit per iteration for the whole batch
+            parts = self._refine(branch_cloud, parts)
         if self.segment_cloud:  # each cloud against its own trees, one call
             self._segment(batch, parts)
         if self.view_model_output or self.view_skeletons:

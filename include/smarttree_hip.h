@@ -37,7 +37,8 @@ extern "C" {
  * 111: st_segment_points_seg and its size query added (no existing signature changed).
  * 112: st_brick_pyramid_need, the st_sparse_conv_{mfma,b3,f16}_list_fwd calls, st_pointwise_mlp_heads_keep and st_move_rows_list
  * added; st_abi_entries(3) added (no existing signature or st_abi_entries value changed).
- * 113: st_fit_tubes and its size query added (no existing signature changed). */
+ * 113: st_fit_tubes and its size query added (no existing signature changed).
+ * 114: st_tree_tally and its size query added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -632,6 +633,32 @@ int64_t st_fit_tubes_workspace_bytes(int64_t n, int64_t m);
 int st_fit_tubes(const float* pts, int64_t n, const int32_t* tube, const float* a, const float* b, const float* r1, const float* r2,
                  int64_t m, float max_relative, int64_t min_points, double min_spread, int64_t* moments, double* fit, void* ws,
                  int64_t ws_bytes, void* stream);
+
+/* ---- inventory: what every tree of a segmented cloud occupies (csrc/tree_tally.hip) --------------------------------------
+ * replaces: nothing -- the reference measures no tree (BranchSkeleton.length / TreeSkeleton.length are its only quantities).
+ *
+ * pts [n,3]; tree [n] int32, the row of the point's tree among n_trees = T (a batch: rows of all its clouds' trees); cls [n] uint8
+ * or NULL (NULL: one class, n_classes is read as 1 and every point is class 0).  Point i takes part when its three coordinates
+ * are finite, 0 <= tree[i] < T and (cls == NULL or cls[i] < n_classes).
+ * box [6*T] float32: per tree the minimum then the maximum of x, y, z over its points, compared through the order-preserving
+ *   integer map of the float's bits (-0 orders below +0); a tree without points keeps (+inf x3, -inf x3).
+ * counts [T*n_classes] int64: points per tree and class.
+ * Cell of a point, in its tree's own box, float32 without contraction: i_k = (int)floorf((p_k - min_k) / cell), clamped to
+ *   [0, 16383].  up in 0..2 is the vertical axis (the package's convention is 1); the point's layer is min(i_up, layers - 1).
+ * area_cells [T] int64: the distinct pairs of the two horizontal indices among the tree's points.
+ * profile [T*layers] int64: per layer the distinct index triples whose layer it is; triples above the last layer stay distinct
+ *   and are counted in the last layer.
+ * Every output may be NULL; a NULL area_cells or profile skips that family of keys.  All outputs are integers or extrema: identical
+ * bits from run to run, and for a batch and its clouds taken alone (a tree's rows depend on its own points only).
+ * Enqueue-only, no read-back.  n = 0 or T = 0 launches nothing beyond the fills of the outputs.  Refused, nothing launched or
+ * written: n outside [0, 2^31), T outside [0, 2^21), layers outside [1, 4096], up outside 0..2, a cell that is not finite or not
+ * > 0, n_classes outside [1, 255], a NULL pts or tree with n > 0 (-1); a workspace below st_tree_tally_workspace_bytes(n, T, layers)
+ * (-2; the size query returns -1 for sizes the call refuses).  The workspace holds the set of distinct cells at its worst case,
+ * every point in a cell of its own in both families, at most half full: 32 bytes per point rounded up to a power of two. */
+int64_t st_tree_tally_workspace_bytes(int64_t n, int64_t n_trees, int layers);
+int st_tree_tally(const float* pts, int64_t n, const int32_t* tree, const uint8_t* cls, int n_classes, int64_t n_trees, int up,
+                  float cell, int layers, float* box, int64_t* counts, int64_t* area_cells, int64_t* profile, void* ws,
+                  int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,9 @@ a tree and a branch of the post-processed skeleton (segmentation.py) and keeps t
 Additive: `refine_skeletons=True` fits the post-processed skeleton's radii and axes to the points the network called wood
 (refine.py); the refined skeleton is what is returned, segmented, drawn and saved, `last_raw_skeleton` / `last_fit` keep the
 skeleton as it was and the per-tube report, and `save_outputs` also writes `skeleton_fit.npz`.
+Additive: `measure_trees=True` measures every tree of the final skeleton on the preprocessed cloud (inventory.py: height, DBH,
+crown extent, wood volume per tree and per branch), segmenting first when `segment_cloud` was not asked for; the result is kept in
+`last_inventory` and `save_outputs` also writes `inventory.json`, `trees.csv` and `branches.csv`.
 """
 from __future__ import annotations
 
@@ -31,7 +34,8 @@ class Pipeline:
                  smooth_kernel_size=0, prune_skeletons=False, min_skeleton_radius=0.0, min_skeleton_length=1000,
                  view_model_output=False, view_skeletons=False, save_outputs=False, save_path="/", branch_classes=[0],
                  cmap=[[1, 0, 0], [0, 1, 0]], device=torch.device("cuda:0"), view_path=None, segment_cloud=False,
-                 segment_max_distance=None, refine_skeletons=False, refine_iterations=2, refine_max_relative=0.5):
+                 segment_max_distance=None, refine_skeletons=False, refine_iterations=2, refine_max_relative=0.5,
+                 measure_trees=False, inventory_cell=0.1, inventory_layers=256):
         self.preprocessing = preprocessing
         self.model_inference = model_inference
         self.skeletonizer = skeletonizer
@@ -59,6 +63,10 @@ class Pipeline:
         self.refine_max_relative = refine_max_relative
         self.last_raw_skeleton = None
         self.last_fit = None
+        self.measure_trees = measure_trees
+        self.inventory_cell = inventory_cell
+        self.inventory_layers = inventory_layers
+        self.last_inventory = None
 
     def process_cloud(self, path: Path = None, cloud: Cloud = None) -> DisjointTreeSkeleton:
         cloud = load_cloud(path) if path is not None else cloud
@@ -78,6 +86,8 @@ class Pipeline:
         if self.segment_cloud:
             self._segment(cloud, skeleton)
             self._segmented = (cloud, self.last_segmentation)
+        if self.measure_trees:
+            self._measure(cloud, skeleton)
         if self.view_model_output or self.view_skeletons:
             if self.view_path is None:
                 raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")
@@ -97,6 +107,8 @@ class Pipeline:
                 save_segmentation(sp, cloud, self.last_segmentation)
             if self.refine_skeletons:
                 self.last_fit.save(sp / "skeleton_fit.npz")
+            if self.measure_trees:
+                self.last_inventory.save(sp)
         return skeleton
 
     def _refine(self, branch_cloud: Cloud, skeleton):
@@ -115,6 +127,17 @@ class Pipeline:
 
         with profiling.stage("segment_cloud"):
             self.last_segmentation = segment_cloud(cloud, skeleton, max_distance=self.segment_max_distance, device=self.device)
+
+    def _measure(self, cloud: Cloud, skeleton) -> None:
+        """Every tree of the skeleton (or of the skeletons of a batch) measured on the cloud `preprocessing` returned: one call."""
+        from .inventory import measure_trees
+        from .segmentation import segment_cloud
+
+        with profiling.stage("measure_trees"):
+            seg = self.last_segmentation if self.segment_cloud else segment_cloud(cloud, skeleton, max_distance=self.segment_max_distance,
+                                                                                  device=self.device)
+            self.last_inventory = measure_trees(cloud, skeleton, segmentation=seg, cell=self.inventory_cell, layers=self.inventory_layers,
+                                                device=self.device)
 
     def process_clouds(self, clouds) -> list:
         """B independent clouds through ONE set of kernel launches (additive; the reference's unit of work is a batch
@@ -144,6 +167,8 @@ class Pipeline:
             parts = self._refine(branch_cloud, parts)
         if self.segment_cloud:  # each cloud against its own trees, one call
             self._segment(batch, parts)
+        if self.measure_trees:  # the whole batch in one call; `last_inventory.split()` gives the clouds' parts
+            self._measure(batch, parts)
         if self.view_model_output or self.view_skeletons:
             if self.view_path is None:
                 raise NotImplementedError("viewing needs open3d, which is out of scope of smart_tree_amd")

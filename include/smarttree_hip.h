@@ -38,7 +38,8 @@ extern "C" {
  * 112: st_brick_pyramid_need, the st_sparse_conv_{mfma,b3,f16}_list_fwd calls, st_pointwise_mlp_heads_keep and st_move_rows_list
  * added; st_abi_entries(3) added (no existing signature or st_abi_entries value changed).
  * 113: st_fit_tubes and its size query added (no existing signature changed).
- * 114: st_tree_tally and its size query added (no existing signature changed). */
+ * 114: st_tree_tally and its size query added (no existing signature changed).
+ * 115: st_ground_extent, st_ground_model, st_ground_height and their size query added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -659,6 +660,65 @@ int64_t st_tree_tally_workspace_bytes(int64_t n, int64_t n_trees, int layers);
 int st_tree_tally(const float* pts, int64_t n, const int32_t* tree, const uint8_t* cls, int n_classes, int64_t n_trees, int up,
                   float cell, int layers, float* box, int64_t* counts, int64_t* area_cells, int64_t* profile, void* ws,
                   int64_t ws_bytes, void* stream);
+
+/* ---- terrain: a ground raster under a cloud, ground points and height above ground (csrc/ground.hip) ----------------------
+ * replaces: nothing -- the reference's clouds hold trees only and it has no notion of terrain.
+ * A progressive morphological filter (Zhang et al. 2003) on a raster of per-cell minima.  Every step is a minimum, a maximum, one
+ * float32 subtraction or one comparison: the outputs are identical bits from run to run, and for a batch and its clouds alone.
+ *
+ * Batch: seg_off [nseg + 1] int32 (device) gives the clouds of the points (NULL with nseg = 1), 1 <= nseg <= st_abi_entries(2).
+ * Every cloud has a raster of its own; the rasters lie one behind the other, cloud s at cell_off[s] (int64 [nseg + 1], HOST).
+ * up in 0..2 is the vertical axis; the plan axes a < b are the other two.  A point takes part when its three coordinates are
+ * finite.  "Ordered" means compared through the order-preserving integer map of the float's bits (-0 below +0).
+ * origin [2 * nseg] float32 (device): per cloud the ordered minimum of the a and of the b coordinate of its participating points.
+ * Cell of a point: ia = (int)floorf((pa - a0) / cell), ib likewise -- one float32 subtraction, one float32 division.
+ * dims [2 * nseg] int32: A = max ia + 1, B = max ib + 1 (at most 2^30); the linear index of a cell is ia * B + ib.  A cloud
+ * without a participating point has origin (+inf, +inf) and dims (0, 0).
+ *
+ * st_ground_extent writes origin and dims (both device).  Enqueue-only; workspace st_ground_workspace_bytes(0).
+ *
+ * st_ground_model: origin on the device as st_ground_extent left it; dims [2 * nseg] int32 and cell_off on the HOST; K = n_windows
+ * in 1..16 half-widths w [K] int32 (HOST) in cells, strictly increasing, each in 1..32; thresholds dh [K] float32 (HOST; no NaN).
+ * Writes surface [cells] float32 and flags [cells] uint8: bit 0 = no point in the cell, bit 1 = not ground.
+ *   1. Z[c] = the ordered minimum of the up-coordinates of the points of cell c, +inf for a cell without points (bit 0).  A point
+ *      whose cell is outside dims takes no part (none is with the extent's own answer).
+ *   2. For k = 0 .. K-1, with the square window of half-width w[k] clipped at the raster's edge:
+ *        E[c] = the ordered minimum of Z over the window (+inf is neutral);
+ *        O[c] = the ordered maximum of E over the window over finite E only, +inf when there is none;
+ *        if Z[c] - O[c] > dh[k] (one float32 subtraction, a strict comparison): set bit 1 and Z[c] = O[c].
+ *      All cells of a window read the Z the previous window left.  An empty cell is filled by the first window that reaches data
+ *      (inf - finite > dh; a window reaches 2 w cells, w for E and w for O) and stays +inf when nothing is in reach (inf - inf is
+ *      NaN, which is not greater).
+ *   3. surface = Z after the last window.
+ * Enqueue-only; workspace st_ground_workspace_bytes(cells) (12 bytes per cell; -1 for cells outside [0, 2^26]).
+ *
+ * st_ground_height: m query positions pts [m,3] with their own seg_off (the cloud itself or any other positions) against the
+ * rasters.  Writes height [m] float32, is_ground [m] uint8 and ground [m] float32, each of which may be NULL.
+ *   qa = (pa - a0) / cell; ia = (int)floorf(qa) clamped into [0, A - 1]; ib likewise; own = surface[ia, ib].
+ *   is_ground = (p_up - own <= tol): one float32 subtraction.
+ *   fa = qa - 0.5f, i0 = floorf(fa), ta = fa - i0 (single float32 operations in this order), likewise fb, j0, tb; the indices i0,
+ *   i0 + 1, j0, j0 + 1 are clamped into the raster (as floats, before the conversion); a sample that is not finite is replaced
+ *   by own; s0 = S[i0,j0] + tb (S[i0,j1] - S[i0,j0]), s1 = S[i1,j0] + tb (S[i1,j1] - S[i1,j0]), ground = s0 + ta (s1 - s0),
+ *   height = p_up - ground, in float32 without contraction.
+ *   A point that does not take part, one of a cloud without cells, or one whose own cell is +inf: height and ground NaN,
+ *   is_ground 0.
+ * Enqueue-only, no workspace.
+ *
+ * Refused by all three, nothing launched or written (-1; the text starts with "ground_extent:", "ground_model:" or
+ * "ground_height:"): a cell that is not finite or not > 0, up outside 0..2, nseg outside [1, st_abi_entries(2)] or nseg > 1 without
+ * seg_off, points outside [0, 2^31), NULL points with n > 0, NULL outputs (extent) or NULL surface / flags with cells > 0; by model
+ * and height: NULL origin, dims or cell_off, a side outside [0, 16384] or only one side 0, more than 2^26 cells, a cell_off that
+ * is not the running sum of A * B from 0; by model: K outside 1..16, windows not strictly increasing or outside 1..32, a NaN
+ * threshold; by height: a NaN tol.  A workspace below the size query's answer: -2. */
+int64_t st_ground_workspace_bytes(int64_t cells);
+int st_ground_extent(const float* pts, int64_t n, const int32_t* seg_off, int nseg, int up, float cell, float* origin, int32_t* dims,
+                     void* ws, int64_t ws_bytes, void* stream);
+int st_ground_model(const float* pts, int64_t n, const int32_t* seg_off, int nseg, int up, float cell, const float* origin,
+                    const int32_t* dims_host, const int64_t* cell_off_host, int n_windows, const int32_t* w_host, const float* dh_host,
+                    float* surface, uint8_t* flags, void* ws, int64_t ws_bytes, void* stream);
+int st_ground_height(const float* pts, int64_t m, const int32_t* seg_off, int nseg, int up, float cell, float tol, const float* origin,
+                     const int32_t* dims_host, const int64_t* cell_off_host, const float* surface, float* height, uint8_t* is_ground,
+                     float* ground, void* stream);
 
 #ifdef __cplusplus
 }

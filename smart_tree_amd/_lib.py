@@ -145,6 +145,10 @@ SIGNATURES = {
     "st_fit_tubes": (c_int, [P, I64, P, P, P, P, P, I64, c_float, I64, c_double, P, P, P, I64, P]),
     "st_tree_tally_workspace_bytes": (I64, [I64, I64, c_int]),
     "st_tree_tally": (c_int, [P, I64, P, P, c_int, I64, c_int, c_float, c_int, P, P, P, P, P, I64, P]),
+    "st_ground_workspace_bytes": (I64, [I64]),
+    "st_ground_extent": (c_int, [P, I64, P, c_int, c_int, c_float, P, P, P, I64, P]),
+    "st_ground_model": (c_int, [P, I64, P, c_int, c_int, c_float, P, P, P, c_int, P, P, P, P, P, I64, P]),
+    "st_ground_height": (c_int, [P, I64, P, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P, P]),
 }
 
 
@@ -172,6 +176,7 @@ ENQUEUE_ONLY = frozenset({
     "st_render_workspace_bytes", "st_render_clear", "st_render_points", "st_render_segments", "st_render_resolve",
     "st_bridge_components_workspace_bytes", "st_segment_workspace_bytes", "st_segment_points_seg",
     "st_fit_tubes_workspace_bytes", "st_fit_tubes", "st_tree_tally_workspace_bytes", "st_tree_tally",
+    "st_ground_workspace_bytes", "st_ground_extent", "st_ground_model", "st_ground_height",
     "st_sparse_conv_mfma_list_fwd", "st_sparse_conv_b3_list_fwd", "st_sparse_conv_f16_list_fwd", "st_pointwise_mlp_heads_keep", "st_move_rows_list",
 })
 

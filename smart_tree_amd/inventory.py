@@ -216,8 +216,9 @@ def tree_columns(n_classes: int) -> tuple:
     return TREE_HEAD + tuple(f"points_class_{k}" for k in range(n_classes)) + TREE_TAIL
 
 
-def tree_table(flat: _Flat, branches, box, counts, area_cells, profile, cell, breast_height=1.3, up=1):
-    """float64 [T, 3 + C + 17] (`tree_columns(C)`) from the tallies (host arrays) and the branch table."""
+def tree_table(flat: _Flat, branches, box, counts, area_cells, profile, cell, breast_height=1.3, up=1, ground_base=None):
+    """float64 [T, 3 + C + 17] (`tree_columns(C)`) from the tallies (host arrays) and the branch table.  `ground_base` [T] (or None):
+    the terrain under every tree's root; where it is finite it is the tree's base instead of its lowest point."""
     T, C = len(flat.tree_rows), counts.shape[1]
     cols = tree_columns(C)
     at = {name: k for k, name in enumerate(cols)}
@@ -231,9 +232,12 @@ def tree_table(flat: _Flat, branches, box, counts, area_cells, profile, cell, br
         out[r, 3:3 + C] = counts[r]
         ends = np.concatenate([flat.xyz[o:o + n, up] for o, n in flat.rows[mine, 4:6].tolist()] or [np.zeros(0)])
         base = box[r, up] if n_pts else (ends.min() if len(ends) else np.nan)
+        low = box[r, up]
+        if ground_base is not None and np.isfinite(ground_base[r]):
+            base = low = float(ground_base[r])
         out[r, at["base"]] = base
         if n_pts:
-            out[r, at["height"]] = box[r, 3 + up] - box[r, up]
+            out[r, at["height"]] = box[r, 3 + up] - low
             out[r, at["crown_width"]] = max(box[r, 3 + h0] - box[r, h0], box[r, 3 + h1] - box[r, h1])
         out[r, at["crown_area"]] = float(area_cells[r]) * cell * cell
         out[r, at["crown_volume"]] = float(profile[r].sum()) * cell * cell * cell
@@ -356,12 +360,26 @@ def point_rows(flat: _Flat, tree_id, seg_off=None, device=None) -> torch.Tensor:
     return torch.from_numpy(table).to(dev).index_select(0, slot)
 
 
+def root_positions(flat: _Flat, branches) -> np.ndarray:
+    """float64 [T,3]: the first vertex of every tree's root branch (the first of order 0), NaN for a tree without one."""
+    out = np.full((len(flat.tree_rows), 3), np.nan)
+    for r in range(len(flat.tree_rows)):
+        mine = np.flatnonzero(flat.tree_of_branch == r)
+        roots = mine[(branches[mine, 4] == 0) & (flat.rows[mine, 5] > 0)]
+        if len(roots):
+            out[r] = flat.xyz[flat.rows[roots[0], 4]]
+    return out
+
+
 def measure_trees(cloud, skeleton, segmentation=None, cell=0.1, layers=256, breast_height=1.3, up=1, max_distance=None,
-                  device=None) -> TreeInventory:
+                  device=None, ground=None) -> TreeInventory:
     """Every tree of `skeleton` measured on the points of `cloud` segmented onto it.  Takes what `segment_cloud` takes: a `Cloud` or
     [n,3] points with a `TreeSkeleton`, a `DisjointTreeSkeleton` or the flat arrays of `save_skeleton_npz`; a collated `Cloud` with a
     list of skeletons, one per cloud.  `segmentation`: the `CloudSegmentation` of these points and this skeleton when the caller has
-    it (else `segment_cloud` runs here, with `max_distance`).  One tally call and one read-back for the whole batch."""
+    it (else `segment_cloud` runs here, with `max_distance`).  One tally call and one read-back for the whole batch.
+    `ground`: the `terrain.GroundModel` of these clouds, in their frame.  A tree's `base` is then the terrain under the first vertex of
+    its root branch (`ground.surface_at`), and `height` and the level of the DBH follow from it; where the terrain is unknown there
+    (NaN) the base stays the tree's lowest point.  None changes nothing."""
     from .segmentation import segment_cloud
 
     if isinstance(cloud, Cloud):
@@ -401,7 +419,16 @@ def measure_trees(cloud, skeleton, segmentation=None, cell=0.1, layers=256, brea
     box = host.view(np.float32).reshape(T, 6)
     counts = counts[:, :_used_classes(counts)]
     branches, orphans = branch_table(flat, segmentation.branches[:, 5])
-    trees = tree_table(flat, branches, box, counts, area_cells, profile, float(cell), float(breast_height), int(up))
+    ground_base = None
+    if ground is not None:
+        if ground.up != int(up) or ground.n_clouds != n_clouds:
+            raise ValueError(f"measure_trees: a ground model of {ground.n_clouds} cloud(s) with up={ground.up} for {n_clouds} cloud(s) with up={up}")
+        roots, ground_base = root_positions(flat, branches), np.full(T, np.nan)
+        for c in range(n_clouds):
+            sel = np.flatnonzero((flat.tree_rows[:, 0] == c) & np.isfinite(roots).all(1))
+            if len(sel):
+                ground_base[sel] = ground.surface_at(roots[sel].astype(np.float32), cloud=c).cpu().numpy()
+    trees = tree_table(flat, branches, box, counts, area_cells, profile, float(cell), float(breast_height), int(up), ground_base)
     return TreeInventory(trees, branches, profile, float(cell), tree_columns(counts.shape[1]), orphans, float(breast_height), int(up), n_clouds)
 
 

@@ -14,6 +14,9 @@ skeleton as it was and the per-tube report, and `save_outputs` also writes `skel
 Additive: `measure_trees=True` measures every tree of the final skeleton on the preprocessed cloud (inventory.py: height, DBH,
 crown extent, wood volume per tree and per branch), segmenting first when `segment_cloud` was not asked for; the result is kept in
 `last_inventory` and `save_outputs` also writes `inventory.json`, `trees.csv` and `branches.csv`.
+Additive: `remove_ground=True` models the terrain under the preprocessed cloud (terrain.py) and takes the ground points out before the
+network sees the cloud, so that everything downstream works on the cloud without ground; the model is kept in `last_ground`,
+`measure_trees` takes the trees' bases from it, and `save_outputs` also writes `ground.npz` and `dtm.asc`.
 """
 from __future__ import annotations
 
@@ -35,7 +38,8 @@ class Pipeline:
                  view_model_output=False, view_skeletons=False, save_outputs=False, save_path="/", branch_classes=[0],
                  cmap=[[1, 0, 0], [0, 1, 0]], device=torch.device("cuda:0"), view_path=None, segment_cloud=False,
                  segment_max_distance=None, refine_skeletons=False, refine_iterations=2, refine_max_relative=0.5,
-                 measure_trees=False, inventory_cell=0.1, inventory_layers=256):
+                 measure_trees=False, inventory_cell=0.1, inventory_layers=256, remove_ground=False, ground_cell=0.5,
+                 ground_max_window=8.0, ground_slope=0.3, ground_tolerance=0.2):
         self.preprocessing = preprocessing
         self.model_inference = model_inference
         self.skeletonizer = skeletonizer
@@ -67,12 +71,20 @@ class Pipeline:
         self.inventory_cell = inventory_cell
         self.inventory_layers = inventory_layers
         self.last_inventory = None
+        self.remove_ground = remove_ground
+        self.ground_cell = ground_cell
+        self.ground_max_window = ground_max_window
+        self.ground_slope = ground_slope
+        self.ground_tolerance = ground_tolerance
+        self.last_ground = None
 
     def process_cloud(self, path: Path = None, cloud: Cloud = None) -> DisjointTreeSkeleton:
         cloud = load_cloud(path) if path is not None else cloud
         cloud = cloud.to_device(self.device)
         with profiling.stage("preprocess"):
             cloud = self.preprocessing(cloud)
+        if self.remove_ground:
+            cloud = self._without_ground(cloud)
         lc = self.model_inference.forward(cloud).to_device(self.device)
         self.last_labelled_cloud = lc
         with profiling.stage("class_filter"):
@@ -109,7 +121,18 @@ class Pipeline:
                 self.last_fit.save(sp / "skeleton_fit.npz")
             if self.measure_trees:
                 self.last_inventory.save(sp)
+            if self.remove_ground:
+                self.last_ground.save(sp)
         return skeleton
+
+    def _without_ground(self, cloud: Cloud) -> Cloud:
+        """The cloud `preprocessing` returned (one, or a batch: one call) without the points its ground model calls ground."""
+        from .terrain import ground_model
+
+        with profiling.stage("remove_ground"):
+            self.last_ground = ground_model(cloud, cell=self.ground_cell, max_window=self.ground_max_window, slope=self.ground_slope,
+                                            ground_tolerance=self.ground_tolerance, device=self.device)
+            return cloud.filter(~self.last_ground.is_ground)
 
     def _refine(self, branch_cloud: Cloud, skeleton):
         """The skeleton (or the skeletons of a batch) fitted to the points it was made from: the points of `branch_classes`."""
@@ -137,7 +160,7 @@ class Pipeline:
             seg = self.last_segmentation if self.segment_cloud else segment_cloud(cloud, skeleton, max_distance=self.segment_max_distance,
                                                                                   device=self.device)
             self.last_inventory = measure_trees(cloud, skeleton, segmentation=seg, cell=self.inventory_cell, layers=self.inventory_layers,
-                                                device=self.device)
+                                                device=self.device, ground=self.last_ground if self.remove_ground else None)
 
     def process_clouds(self, clouds) -> list:
         """B independent clouds through ONE set of kernel launches (additive; the reference's unit of work is a batch
@@ -153,6 +176,8 @@ class Pipeline:
             batch = self.preprocessing(batch)
         if batch.n_seg != len(clouds):  # an augmentation that rebuilt the Cloud without its batch offsets would merge the inputs
             raise RuntimeError(f"process_clouds: preprocessing returned {batch.n_seg} cloud(s) for a batch of {len(clouds)}")
+        if self.remove_ground:  # one ground model for the whole batch; `last_ground.split()` gives the clouds' parts
+            batch = self._without_ground(batch)
         lc = self.model_inference.forward(batch).to_device(self.device)
         self.last_labelled_cloud = lc
         with profiling.stage("class_filter"):

@@ -39,7 +39,8 @@ extern "C" {
  * added; st_abi_entries(3) added (no existing signature or st_abi_entries value changed).
  * 113: st_fit_tubes and its size query added (no existing signature changed).
  * 114: st_tree_tally and its size query added (no existing signature changed).
- * 115: st_ground_extent, st_ground_model, st_ground_height and their size query added (no existing signature changed). */
+ * 115: st_ground_extent, st_ground_model, st_ground_height and their size query added (no existing signature changed).
+ * 116: the neighbour searches serve a run of queries per wavefront (no signature, workspace size or result changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,

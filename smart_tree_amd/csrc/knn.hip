@@ -12,8 +12,8 @@
 // outlier_removal needs d < r_i): same result, far fewer cells visited for thin branches.
 //
 // Grid: dense cell_start[] over the bounding box (cells capped, cell size doubled until it fits),
-// points counting-sorted by cell into float4 (x, y, z, index) records; one wavefront per query, the K nearest
-// drawn from an LDS candidate list by rank counting.
+// points counting-sorted by cell into float4 (x, y, z, index) records; one wavefront per query (a short run of
+// queries per wavefront, one at a time), the K nearest drawn from an LDS candidate list by rank counting.
 #include "st_common.h"
 #include "st_grid.h"
 
@@ -101,7 +101,9 @@ __global__ void __launch_bounds__(KNN_BLOCK) k_grid_bbox(const float* pts, int64
     }
 }
 
-__global__ void k_grid_dims(StGrid* g, float cell, int64_t max_cells, float r, int nseg, float mean_mult, int64_t n_bound) {
+// ncell1_out: cells in use + 1, the device-side length of the cell table for the clear and the scan behind it
+__global__ void k_grid_dims(StGrid* g, float cell, int64_t max_cells, float r, int nseg, float mean_mult, int64_t n_bound,
+                            int64_t* ncell1_out) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float lo[3], hi[3];
     for (int a = 0; a < 3; a++) { lo[a] = st_ord2f(g->lo_ord[a]); hi[a] = st_ord2f(g->hi_ord[a]); g->lo[a] = lo[a]; }
@@ -138,11 +140,11 @@ __global__ void k_grid_dims(StGrid* g, float cell, int64_t max_cells, float r, i
     g->dim[0] = g->seg_dim0 * nseg;  // every cloud gets its own slab of cells along x
     g->cell = cell;
     g->ncell = (int64_t)g->dim[0] * g->dim[1] * g->dim[2];
+    *ncell1_out = g->ncell + 1;
 }
 
 // The counting pass hands every point its rank inside its cell (the value its atomicAdd returns), so the fill pass needs
 // neither a second round of atomics nor a cursor copy of the (tens of millions of words long) cell table.
-__global__ void k_grid_ncell1(const StGrid* g, int64_t* out) { *out = g->ncell + 1; }
 
 __global__ void __launch_bounds__(KNN_BLOCK) k_grid_count(const float* pts, int64_t n, const StGrid* g, uint32_t* counts,
                                                           const int* seg_off, int nseg, uint32_t* pt_cell, uint32_t* pt_rank,
@@ -208,7 +210,7 @@ int st_grid_build(const float* pts, int64_t n, float cell, int64_t max_cells, St
                            dim3(KNN_BLOCK), 0, stream, bound, n_bound, g, nseg > 1 ? (bound_seg_off ? bound_seg_off : seg_off) : (const int*)nullptr,
                            valid);
     hipLaunchKernelGGL(k_grid_dims, dim3(1), dim3(64), 0, stream, g, cell, ncell, r, nseg, mean_mult,
-                       (r < 0.0f && bound) ? n_bound : (int64_t)0);
+                       (r < 0.0f && bound) ? n_bound : (int64_t)0, ncell1_dev);
     if (getenv("ST_GRID_DEBUG")) {
         StGrid h;
         (void)hipMemcpyAsync(&h, g, sizeof(StGrid), hipMemcpyDeviceToHost, stream);
@@ -217,8 +219,7 @@ int st_grid_build(const float* pts, int64_t n, float cell, int64_t max_cells, St
                 (long long)ncell, h.dim[0], h.dim[1], h.dim[2]);
     }
     // the cell table is cleared and scanned over the cells the grid really has (g->ncell + 1, a device-side number), not over
-    // the host's bound: a batch of 16 clouds is bounded at 134M cells and uses 18M
-    hipLaunchKernelGGL(k_grid_ncell1, dim3(1), dim3(1), 0, stream, (const StGrid*)g, ncell1_dev);
+    // the host's bound: a batch of 16 clouds is bounded at 134M cells and uses 18M (k_grid_dims has left that number in ncell1_dev)
     st_fill_u32_dev(cell_start, ncell + 1, ncell1_dev, 0u, stream);
     hipLaunchKernelGGL(k_grid_count, dim3(gb), dim3(KNN_BLOCK), 0, stream, pts, n, (const StGrid*)g, cell_start, seg_off, nseg,
                        pt_cell, pt_rank, valid);
@@ -233,7 +234,7 @@ int st_grid_build(const float* pts, int64_t n, float cell, int64_t max_cells, St
 
 // mode 0: no per-query bound; 1: keep sqrtf(d2) <= bound[i]; 2: keep sqrtf(d2) < bound[i]
 //
-// One WAVEFRONT per query.  A 50k-point cloud with a lane (or a few lanes) per query is a handful of
+// One WAVEFRONT per query at a time.  A 50k-point cloud with a lane (or a few lanes) per query is a handful of
 // wavefronts per SIMD, each walking a long chain of dependent loads; with a wavefront per query there are
 // 50k of them and every step is 64 wide:
 //   1. lanes take the (x, y) rows of grid cells around the query (cells along z are contiguous in memory, so a
@@ -306,6 +307,43 @@ __device__ __forceinline__ int knn_cut(unsigned long long* keys, int n, int lane
     return n < K ? n : K;
 }
 
+// A wavefront serves a RUN of KNN_QW consecutive queries, one after the other (see k_knn): the loads in front of a search are
+// paid once per run, and the cell rows of the next query are requested under the candidate loop of the current one.  The result
+// does not depend on it (2, 4 and 8 measured: profiles/knn_runs_ab.txt).
+#ifndef KNN_QW
+#define KNN_QW 8
+#endif
+static_assert(KNN_QW >= 1 && KNN_QW <= 64, "one lane per query of the run resolves it");
+
+// what a search needs of its query, resolved at the head of the run by the lane that owns the query and kept in LDS (16 words)
+// until the query's turn
+struct __attribute__((aligned(16))) KnnQ {
+    float px, py, pz, r2, d2_max, rs2;
+    int x0, y0, ny, nym, nrows, z0, z1, xoff;  // box of cells (x0.., ny rows along y, nrows (x, y) rows in all), nym: knn_rows_div
+    unsigned i;                                // the query's original index (cell order; otherwise it is the query's number)
+    int act;                                   // 0: no query (past the end of the run)
+};
+
+// the same value in every lane -> a scalar (what the compiler cannot know of a value read from LDS)
+__device__ __forceinline__ float knn_uni_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ int knn_uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ KnnQ knn_uni(const KnnQ& v) {
+    KnnQ Q;
+    Q.px = knn_uni_f(v.px); Q.py = knn_uni_f(v.py); Q.pz = knn_uni_f(v.pz);
+    Q.r2 = knn_uni_f(v.r2); Q.d2_max = knn_uni_f(v.d2_max); Q.rs2 = knn_uni_f(v.rs2);
+    Q.x0 = knn_uni_i(v.x0); Q.y0 = knn_uni_i(v.y0); Q.ny = knn_uni_i(v.ny); Q.nym = knn_uni_i(v.nym);
+    Q.nrows = knn_uni_i(v.nrows); Q.z0 = knn_uni_i(v.z0); Q.z1 = knn_uni_i(v.z1); Q.xoff = knn_uni_i(v.xoff);
+    Q.i = (unsigned)knn_uni_i((int)v.i);
+    Q.act = knn_uni_i(v.act);
+    return Q;
+}
+
+// t / ny for 0 <= t < ny + 65 without an integer division: ny >= 64 makes it 0 or 1; below that t < 128 and the 16-bit
+// reciprocal nym = 65536 / ny + 1 is exact (nym * ny = 65536 + e with 0 < e <= ny, the quotient is off only if t * e >= 65536)
+__device__ __forceinline__ int knn_rows_div(int t, int ny, int nym) {
+    return ny >= 64 ? (t >= ny ? 1 : 0) : (int)(((unsigned)t * (unsigned)nym) >> 16);
+}
+
 // COUNT = true: only "does the query have at least K neighbours (itself included) inside its bound?" -- the whole of
 // outlier_removal (filter.py:6-11: all nb_points slots filled).  No key list, no ranking, and the scan stops at the K-th hit;
 // idx_out is then a byte mask [n1].  The predicates are the search's own, so the mask equals idx[:, K-1] != -1.
@@ -319,154 +357,211 @@ __global__ void __launch_bounds__(KNN_BLOCK, 8) k_knn(const float* __restrict__ 
     __shared__ uint32_t s_roff[KNN_WAVES][65], s_rfirst[KNN_WAVES][64];
     __shared__ unsigned long long s_rmask[KNN_WAVES][KNN_MASK_WORDS];  // bit p of word w: a (non-empty) row's candidates start at 64 w + p
     __shared__ __attribute__((aligned(16))) unsigned long long s_keys[KNN_WAVES][KNN_CAP];
+    __shared__ KnnQ s_head[KNN_WAVES][KNN_QW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int64_t i = (int64_t)blockIdx.x * KNN_WAVES + wave;
-    if (i >= n1) return;  // wave-uniform; the kernel has no workgroup barrier
+    const int64_t base = ((int64_t)blockIdx.x * KNN_WAVES + wave) * KNN_QW;  // first query of this wavefront's run
+    if (base >= n1) return;  // wave-uniform; the kernel has no workgroup barrier
     // valid (optional, with src == dst): only the points with valid[j] != 0 are part of the search -- the table holds only them, and
-    // only they are queried (cell order: the table's total is the number of queries; the caller has cleared the output)
-    if (valid && (cell_order ? i >= (int64_t)cell_start[g->ncell] : !valid[i])) return;
-    // cell_order (src IS dst): wavefront p takes the p-th record of the cell-sorted point list instead of point p, so
-    // neighbouring wavefronts search the same cells (their rows stay in L1 / L2); rows are written by original index, the
-    // result does not depend on which wavefront computed it
-    // (the record carries the point's coordinates as well: one dependent load less before the cell rows can be requested)
-    float px, py, pz;
-    if (cell_order) {
-        const float4 me = recs[i];
-        px = me.x; py = me.y; pz = me.z;
-        i = (int64_t)__float_as_uint(me.w);
-    } else {
-        px = src[3 * i]; py = src[3 * i + 1]; pz = src[3 * i + 2];
+    // only they are queried (cell order: the table's total is the number of queries, read once per wavefront; the caller has
+    // cleared the output)
+    int64_t nq = n1;
+    if (valid && cell_order) {
+        const int64_t in_table = (int64_t)cell_start[g->ncell];
+        if (in_table < nq) nq = in_table;
+        if (base >= nq) return;  // wave-uniform
     }
     uint32_t* roff = s_roff[wave];
     uint32_t* rfirst = s_rfirst[wave];
     unsigned long long* rmask = s_rmask[wave];
     unsigned long long* keys = s_keys[wave];
-    const int seg = st_seg_find(seg_off, nseg, i);  // wave-uniform: one query per wavefront
-    if (r < 0.0f) r = g->seg_r[seg];  // radius reduced on the device (st_knn_radius with r < 0): max(bound) over the query's cloud
-    const float r2 = r * r;
-    float reach_r = r;
-    // The per-query bound is defined on the rounded root -- sqrtf(d2) <= bound (mode 1) or < bound (mode 2), graph.py:38-40 /
-    // filter.py:9-10 -- and sqrtf is monotone, so it is the same as d2 <= d2_max with d2_max = the largest float whose root
-    // still passes: found once per query (a few steps around bound^2), and no candidate needs a root.
-    float d2_max = __uint_as_float(0x7f800000u);
-    if (mode != 0) {
-        const float bnd = bound[i];
-        if (bnd < reach_r) reach_r = bnd;
-        d2_max = knn_d2_max(bnd, mode == 2);
+    const float cell = g->cell, lo0 = g->lo[0], lo1 = g->lo[1], lo2 = g->lo[2];
+    const int seg_dim0 = g->seg_dim0, dim1 = g->dim[1], dim2 = g->dim[2];
+    // ---- head of the run: lane q < KNN_QW resolves query base + q -- its record, bound, cloud, radius, d2_max and box of cells --
+    // so the dependent loads in front of a search (record -> bound, cloud offsets -> cloud radius) are one chain per RUN, all its
+    // queries side by side, and the scalar work per query (knn_d2_max's roots, the cell of the query) runs once, in one lane.
+    // Every load is guarded by the lane's own query index: a ragged last run reads nothing past recs / src / bound / valid.
+    // cell_order (src IS dst): the run is KNN_QW consecutive records of the cell-sorted point list instead of consecutive points,
+    // so its queries (and the neighbouring wavefronts') search the same cells (their rows stay in L1 / L2); rows are written by
+    // original index, the result does not depend on which wavefront computed it
+    // (the record carries the point's coordinates as well: one dependent load less before the cell rows can be requested)
+    KnnQ h;  // this LANE's query (h.act = 0: none)
+    h.px = h.py = h.pz = h.r2 = h.rs2 = 0.0f;
+    h.d2_max = -1.0f;
+    h.x0 = h.y0 = h.ny = h.nym = h.nrows = h.z0 = h.z1 = h.xoff = h.act = 0;
+    h.i = 0;
+    if (lane < KNN_QW && base + lane < nq && !(valid && !cell_order && !valid[base + lane])) {
+        int64_t i = base + lane;
+        float px, py, pz;
+        if (cell_order) {
+            const float4 me = recs[i];
+            px = me.x; py = me.y; pz = me.z;
+            i = (int64_t)__float_as_uint(me.w);
+        } else {
+            px = src[3 * i]; py = src[3 * i + 1]; pz = src[3 * i + 2];
+        }
+        const int seg = st_seg_find(seg_off, nseg, i);
+        const float rq = r < 0.0f ? g->seg_r[seg] : r;  // radius reduced on the device (st_knn_radius with r < 0): max(bound) over the query's cloud
+        float reach_r = rq;
+        // The per-query bound is defined on the rounded root -- sqrtf(d2) <= bound (mode 1) or < bound (mode 2), graph.py:38-40 /
+        // filter.py:9-10 -- and sqrtf is monotone, so it is the same as d2 <= d2_max with d2_max = the largest float whose root
+        // still passes: found once per query (a few steps around bound^2), and no candidate needs a root.
+        float d2_max = __uint_as_float(0x7f800000u);
+        if (mode != 0) {
+            const float bnd = bound[i];
+            if (bnd < reach_r) reach_r = bnd;
+            d2_max = knn_d2_max(bnd, mode == 2);
+        }
+        const float reach_f = reach_r > 0.0f ? ceilf(reach_r / cell) : 0.0f;
+        int reach = reach_f < 1.0e6f ? (int)reach_f : 1000000;  // (an infinite bound reaches every cell; the clamp keeps the integer arithmetic defined)
+        if (reach < 1) reach = 1;
+        // a query with a NaN / infinite coordinate has no neighbours (every distance is NaN or infinite)
+        const bool q_finite = fabsf(px) <= 3.0e38f && fabsf(py) <= 3.0e38f && fabsf(pz) <= 3.0e38f;
+        if (!q_finite) { px = lo0; py = lo1; pz = lo2; reach = 0; d2_max = -1.0f; }
+        const int cx = (int)floorf((px - lo0) / cell), cy = (int)floorf((py - lo1) / cell), cz = (int)floorf((pz - lo2) / cell);
+        const int x0 = st_max(cx - reach, 0), x1 = st_min(cx + reach, seg_dim0 - 1);
+        const int y0 = st_max(cy - reach, 0), y1 = st_min(cy + reach, dim1 - 1);
+        const int z0 = st_max(cz - reach, 0), z1 = st_min(cz + reach, dim2 - 1);
+        // rows (x, y) farther than the search radius in the xy-plane are skipped and the z-range of the others
+        // is clipped to the sphere (a slightly inflated radius keeps the pruning conservative)
+        const float rs = reach_r * 1.0001f + 1e-7f;
+        const int ny = y1 - y0 + 1;
+        h.px = px; h.py = py; h.pz = pz;
+        h.r2 = rq * rq; h.d2_max = d2_max; h.rs2 = rs * rs;
+        h.x0 = x0; h.y0 = y0; h.z0 = z0; h.z1 = z1; h.ny = ny;
+        h.nym = ny > 0 && ny < 64 ? 65536 / ny + 1 : 0;  // knn_rows_div
+        // d2_max < 0 (a non-finite query; a negative or NaN bound; bound 0 and strict): no candidate can pass, no row is read
+        h.nrows = (x1 >= x0 && ny > 0 && z1 >= z0 && !(d2_max < 0.0f)) ? (x1 - x0 + 1) * ny : 0;
+        h.xoff = seg * seg_dim0;  // the cloud's slab of cells
+        h.i = (unsigned)i;
+        h.act = 1;
     }
-    const float cell = g->cell;
-    const float reach_f = reach_r > 0.0f ? ceilf(reach_r / cell) : 0.0f;
-    int reach = reach_f < 1.0e6f ? (int)reach_f : 1000000;  // (an infinite bound reaches every cell; the clamp keeps the integer arithmetic defined)
-    if (reach < 1) reach = 1;
-    // a query with a NaN / infinite coordinate has no neighbours (every distance is NaN or infinite)
-    const bool q_finite = fabsf(px) <= 3.0e38f && fabsf(py) <= 3.0e38f && fabsf(pz) <= 3.0e38f;
-    if (!q_finite) { px = g->lo[0]; py = g->lo[1]; pz = g->lo[2]; reach = 0; d2_max = -1.0f; }
-    const int cx = (int)floorf((px - g->lo[0]) / cell), cy = (int)floorf((py - g->lo[1]) / cell), cz = (int)floorf((pz - g->lo[2]) / cell);
-    const int xoff = seg * g->seg_dim0;  // the cloud's slab of cells
-    const int x0 = st_max(cx - reach, 0), x1 = st_min(cx + reach, g->seg_dim0 - 1);
-    const int y0 = st_max(cy - reach, 0), y1 = st_min(cy + reach, g->dim[1] - 1);
-    const int z0 = st_max(cz - reach, 0), z1 = st_min(cz + reach, g->dim[2] - 1);
-    // rows (x, y) farther than the search radius in the xy-plane are skipped and the z-range of the others
-    // is clipped to the sphere (a slightly inflated radius keeps the pruning conservative)
-    const float rs = reach_r * 1.0001f + 1e-7f, rs2 = rs * rs;
-    const int ny = y1 - y0 + 1, nrows = (x1 >= x0 && ny > 0 && z1 >= z0) ? (x1 - x0 + 1) * ny : 0;
-    int nkeys = 0;  // wave-uniform
-    // once K keys are known, a candidate that is not smaller than the K-th of them cannot be among the K nearest: it is
-    // dropped before it reaches the list (around a trunk a query sees thousands of points inside its bound)
-    unsigned long long thr = ~0ull;
-    for (int rbase = 0; rbase < nrows && !(COUNT && nkeys >= K); rbase += 64) {
-        const int rowi = rbase + lane;
-        uint32_t first = 0, cnt = 0;
-        if (rowi < nrows) {
-            const int x = x0 + rowi / ny, y = y0 + rowi % ny;
-            const float cx0 = g->lo[0] + (float)x * cell, ex = px < cx0 ? cx0 - px : (px > cx0 + cell ? px - (cx0 + cell) : 0.0f);
-            const float cy0 = g->lo[1] + (float)y * cell, ey = py < cy0 ? cy0 - py : (py > cy0 + cell ? py - (cy0 + cell) : 0.0f);
+    // (kept in LDS, not in registers: sixteen values per lane across the whole search would spill)
+    const KnnQ* head = s_head[wave];
+    if (lane < KNN_QW) s_head[wave][lane] = h;
+    __builtin_amdgcn_wave_barrier();
+    // One chunk of 64 (x, y) rows of query F -- rows rbase + lane, the chunk's row 0 at (x0 + xb, y0 + yb) -- as [first, first + cnt)
+    // ranges of records: the two cell_start loads per row.  REQUESTED one chunk ahead: the next chunk of the same query, or the
+    // first chunk of the run's next query, is asked for before the candidate loop of the current chunk starts and used after it,
+    // so its round trip runs under that loop instead of in front of the next one.
+    auto fetch = [&](const KnnQ& F, int rbase, int xb, int yb, uint32_t& first, uint32_t& cnt) {
+        first = 0; cnt = 0;
+        if (rbase + lane < F.nrows) {
+            const int t = yb + lane, dq = knn_rows_div(t, F.ny, F.nym);
+            const int x = F.x0 + xb + dq, y = F.y0 + (t - dq * F.ny);  // = x0 + rowi / ny, y0 + rowi % ny
+            const float cx0 = lo0 + (float)x * cell, ex = F.px < cx0 ? cx0 - F.px : (F.px > cx0 + cell ? F.px - (cx0 + cell) : 0.0f);
+            const float cy0 = lo1 + (float)y * cell, ey = F.py < cy0 ? cy0 - F.py : (F.py > cy0 + cell ? F.py - (cy0 + cell) : 0.0f);
             const float dxy2 = ex * ex + ey * ey;
-            if (!(dxy2 > rs2)) {
-                const float rz = sqrtf(rs2 - dxy2);
+            if (!(dxy2 > F.rs2)) {
+                const float rz = sqrtf(F.rs2 - dxy2);
                 // (clamped as floats: with an infinite bound rz is infinite and the integer conversion would be undefined)
-                const int za = (int)fmaxf(floorf((pz - rz - g->lo[2]) / cell) - 1.0f, (float)z0),
-                          zb = (int)fminf(floorf((pz + rz - g->lo[2]) / cell) + 1.0f, (float)z1);
+                // (divisions, as st_grid_axis files the points: the cells a query covers stay consistent with the cells points are under)
+                const int za = (int)fmaxf(floorf((F.pz - rz - lo2) / cell) - 1.0f, (float)F.z0),
+                          zb = (int)fminf(floorf((F.pz + rz - lo2) / cell) + 1.0f, (float)F.z1);
                 if (za <= zb) {
-                    const int64_t row = ((int64_t)(xoff + x) * g->dim[1] + y) * g->dim[2];
+                    const int64_t row = ((int64_t)(F.xoff + x) * dim1 + y) * dim2;
                     first = cell_start[row + za];
                     cnt = cell_start[row + zb + 1] - first;
                 }
             }
         }
-        const uint32_t incl = knn_wave_scan(cnt, lane);
-        const int total = (int)__shfl(incl, 63);
-        // The rows of the chunk, EMPTY ONES DROPPED, in LDS (first candidate's number, first record); candidate t belongs to the last
-        // row that starts at or before it.  Found by counting start marks: every row sets one bit (its first candidate's number) in a
-        // mask of the chunk's candidates, and the 64 candidates [cb, cb + 64) read ONE mask word -- rows before cb + marks at or
-        // below the lane.  (A binary search over the row offsets per candidate was six dependent LDS reads; it stays for a chunk
-        // with more candidates than the mask holds.)
-        const unsigned long long nonempty = __ballot(cnt != 0u);
-        const int nr = __popcll(nonempty);  // wave-uniform
-        const int slot = __popcll(nonempty & ((1ull << lane) - 1ull));
-        const bool marks = total <= 64 * KNN_MASK_WORDS;
-        __builtin_amdgcn_wave_barrier();  // the previous chunk's reads of roff / rfirst / rmask are done
-        if (marks)
-            for (int w = lane; w < (total + 63) / 64; w += 64) rmask[w] = 0ull;
-        if (cnt != 0u) { roff[slot] = incl - cnt; rfirst[slot] = first; }
-        if (lane == 63) roff[nr] = incl;
-        __builtin_amdgcn_wave_barrier();
-        if (marks && cnt != 0u) atomicOr(&rmask[(incl - cnt) >> 6], 1ull << ((incl - cnt) & 63u));
-        __builtin_amdgcn_wave_barrier();
-        int rows_before = 0;  // non-empty rows that start before cb (wave-uniform)
-        for (int cb = 0; cb < total && !(COUNT && nkeys >= K); cb += 64) {
-            const int t = cb + lane;
-            bool ok = false;
-            unsigned long long key = 0ull;
-            const unsigned long long starts = marks ? rmask[cb >> 6] : 0ull;  // (one word for the whole wavefront: a broadcast)
-            if (t < total) {
-                int lo;
-                if (marks) {
-                    lo = rows_before + __popcll(starts & (~0ull >> (63 - lane))) - 1;
-                } else {
-                    lo = 0;
-                    int hi = nr;  // row with roff[row] <= t < roff[row + 1]
-                    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (roff[mid] <= (uint32_t)t) lo = mid; else hi = mid; }
+    };
+    uint32_t pf_first = 0, pf_cnt = 0;  // the row chunk requested ahead
+    bool pf_ready = false;              // ... is the first chunk of the query whose turn it is (wave-uniform)
+    for (int q = 0; q < KNN_QW && base + q < nq; q++) {  // wave-uniform
+        const bool has_next = q + 1 < KNN_QW && base + q + 1 < nq;
+        const KnnQ Q = knn_uni(head[q]);  // (one address for the whole wavefront: broadcast reads)
+        if (!pf_ready) fetch(Q, 0, 0, 0, pf_first, pf_cnt);
+        pf_ready = false;
+        const float px = Q.px, py = Q.py, pz = Q.pz, r2 = Q.r2, d2_max = Q.d2_max;
+        const int64_t i = cell_order ? (int64_t)Q.i : base + q;
+        int nkeys = 0;  // wave-uniform
+        // once K keys are known, a candidate that is not smaller than the K-th of them cannot be among the K nearest: it is
+        // dropped before it reaches the list (around a trunk a query sees thousands of points inside its bound)
+        unsigned long long thr = ~0ull;
+        int xb = 0, yb = 0;  // rbase = xb * ny + yb
+        for (int rbase = 0; rbase < Q.nrows && !(COUNT && nkeys >= K); rbase += 64) {
+            const uint32_t first = pf_first, cnt = pf_cnt;
+            {   // request the chunk after this one
+                const int t = yb + 64, dq = knn_rows_div(t, Q.ny, Q.nym);
+                xb += dq; yb = t - dq * Q.ny;
+                const bool more = rbase + 64 < Q.nrows;
+                pf_ready = !more && has_next;
+                if (more) fetch(Q, rbase + 64, xb, yb, pf_first, pf_cnt);
+                else if (has_next) fetch(head[q + 1], 0, 0, 0, pf_first, pf_cnt);
+            }
+            const uint32_t incl = knn_wave_scan(cnt, lane);
+            const int total = (int)__shfl(incl, 63);
+            // The rows of the chunk, EMPTY ONES DROPPED, in LDS (first candidate's number, first record); candidate t belongs to the last
+            // row that starts at or before it.  Found by counting start marks: every row sets one bit (its first candidate's number) in a
+            // mask of the chunk's candidates, and the 64 candidates [cb, cb + 64) read ONE mask word -- rows before cb + marks at or
+            // below the lane.  (A binary search over the row offsets per candidate was six dependent LDS reads; it stays for a chunk
+            // with more candidates than the mask holds.)
+            const unsigned long long nonempty = __ballot(cnt != 0u);
+            const int nr = __popcll(nonempty);  // wave-uniform
+            const int slot = __popcll(nonempty & ((1ull << lane) - 1ull));
+            const bool marks = total <= 64 * KNN_MASK_WORDS;
+            __builtin_amdgcn_wave_barrier();  // the previous chunk's reads of roff / rfirst / rmask are done
+            if (marks)
+                for (int w = lane; w < (total + 63) / 64; w += 64) rmask[w] = 0ull;
+            if (cnt != 0u) { roff[slot] = incl - cnt; rfirst[slot] = first; }
+            if (lane == 63) roff[nr] = incl;
+            __builtin_amdgcn_wave_barrier();
+            if (marks && cnt != 0u) atomicOr(&rmask[(incl - cnt) >> 6], 1ull << ((incl - cnt) & 63u));
+            __builtin_amdgcn_wave_barrier();
+            int rows_before = 0;  // non-empty rows that start before cb (wave-uniform)
+            for (int cb = 0; cb < total && !(COUNT && nkeys >= K); cb += 64) {
+                const int t = cb + lane;
+                bool ok = false;
+                unsigned long long key = 0ull;
+                const unsigned long long starts = marks ? rmask[cb >> 6] : 0ull;  // (one word for the whole wavefront: a broadcast)
+                if (t < total) {
+                    int lo;
+                    if (marks) {
+                        lo = rows_before + __popcll(starts & (~0ull >> (63 - lane))) - 1;
+                    } else {
+                        lo = 0;
+                        int hi = nr;  // row with roff[row] <= t < roff[row + 1]
+                        while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (roff[mid] <= (uint32_t)t) lo = mid; else hi = mid; }
+                    }
+                    const float4 q = recs[rfirst[lo] + ((uint32_t)t - roff[lo])];
+                    const float dx = px - q.x, dy = py - q.y, dz = pz - q.z;
+                    float d2 = dx * dx;
+                    float tt = dy * dy;
+                    d2 = d2 + tt;
+                    tt = dz * dz;
+                    d2 = d2 + tt;
+                    ok = d2 < r2 && d2 <= d2_max;
+                    key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)__float_as_uint(q.w);  // d2 >= 0: bits order like values
+                    if (!COUNT) ok = ok && key < thr;
                 }
-                const float4 q = recs[rfirst[lo] + ((uint32_t)t - roff[lo])];
-                const float dx = px - q.x, dy = py - q.y, dz = pz - q.z;
-                float d2 = dx * dx;
-                float tt = dy * dy;
-                d2 = d2 + tt;
-                tt = dz * dz;
-                d2 = d2 + tt;
-                ok = d2 < r2 && d2 <= d2_max;
-                key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned long long)__float_as_uint(q.w);  // d2 >= 0: bits order like values
-                if (!COUNT) ok = ok && key < thr;
+                const unsigned long long bal = __ballot(ok);
+                if (!COUNT && ok) keys[nkeys + __popcll(bal & ((1ull << lane) - 1ull))] = key;
+                nkeys += __popcll(bal);
+                if (!COUNT && nkeys > KNN_CAP - 64) {
+                    nkeys = knn_cut<K>(keys, nkeys, lane);
+                    if (nkeys == K) thr = keys[K - 1];
+                }
+                rows_before += __popcll(starts);
             }
-            const unsigned long long bal = __ballot(ok);
-            if (!COUNT && ok) keys[nkeys + __popcll(bal & ((1ull << lane) - 1ull))] = key;
-            nkeys += __popcll(bal);
-            if (!COUNT && nkeys > KNN_CAP - 64) {
-                nkeys = knn_cut<K>(keys, nkeys, lane);
-                if (nkeys == K) thr = keys[K - 1];
-            }
-            rows_before += __popcll(starts);
         }
-    }
-    if (COUNT) {
-        if (lane == 0) reinterpret_cast<uint8_t*>(idx_out)[i] = nkeys >= K ? 1 : 0;
-        return;
-    }
-    // output: rank = slot.  (d2, index) ascending, -1 / NaN padding.
-    __builtin_amdgcn_wave_barrier();
-    {
-        auto put = [&](unsigned long long key, int rank) {
-            if (rank < K) {
-                idx_out[i * K + rank] = (int64_t)(unsigned)(key & 0xffffffffull);
-                dist_out[i * K + rank] = sqrtf(__uint_as_float((unsigned)(key >> 32)));
+        if (COUNT) {
+            if (Q.act && lane == 0) reinterpret_cast<uint8_t*>(idx_out)[i] = nkeys >= K ? 1 : 0;
+        } else if (Q.act) {
+            // output: rank = slot.  (d2, index) ascending, -1 / NaN padding.
+            __builtin_amdgcn_wave_barrier();
+            auto put = [&](unsigned long long key, int rank) {
+                if (rank < K) {
+                    idx_out[i * K + rank] = (int64_t)(unsigned)(key & 0xffffffffull);
+                    dist_out[i * K + rank] = sqrtf(__uint_as_float((unsigned)(key >> 32)));
+                }
+            };
+            if (nkeys <= 64) knn_rank<1>(keys, nkeys, lane, put); else knn_rank<KNN_CAP / 64>(keys, nkeys, lane, put);
+            const int found = nkeys < K ? nkeys : K;
+            if (lane >= found && lane < K) {
+                idx_out[i * K + lane] = (int64_t)-1;
+                dist_out[i * K + lane] = __uint_as_float(0x7fc00000u);
             }
-        };
-        if (nkeys <= 64) knn_rank<1>(keys, nkeys, lane, put); else knn_rank<KNN_CAP / 64>(keys, nkeys, lane, put);
-        const int found = nkeys < K ? nkeys : K;
-        if (lane >= found && lane < K) {
-            idx_out[i * K + lane] = (int64_t)-1;
-            dist_out[i * K + lane] = __uint_as_float(0x7fc00000u);
+            __builtin_amdgcn_wave_barrier();  // the key list is the next query's from here on
         }
     }
 }
@@ -530,7 +625,7 @@ extern "C" int st_knn_radius_seg(const float* src, int64_t n1, const float* dst,
     const float cell_arg = cell_hint != 0.0f ? cell_hint : (r >= 0.0f ? r : -1.0f);
     ST_TRY(st_grid_build(dst, n2, cell_arg, knn_cells(n2, nseg), g, cell_start, recs, sub, sub_bytes, stream, r, bound, n1,
                          dst_seg_off, nseg, src_seg_off, cell_hint < 0.0f ? (cell_mean_mult >= 0.0f ? cell_mean_mult : KNN_MEAN_MULT) : 0.0f, nullptr));
-    dim3 grid((unsigned)st_div_up(n1, KNN_WAVES)), block(KNN_BLOCK);
+    dim3 grid((unsigned)st_div_up(n1, (int64_t)KNN_WAVES * KNN_QW)), block(KNN_BLOCK);
     const int cell_order = src == dst && n1 == n2 ? 1 : 0;
     if (K == 1)
         hipLaunchKernelGGL((k_knn<1>), grid, block, 0, stream, src, n1, (const StGrid*)g, (const uint32_t*)cell_start,
@@ -580,7 +675,7 @@ extern "C" int st_radius_count_seg(const float* src, int64_t n1, const float* ds
     ST_TRY(st_grid_build(dst, n2, cell_arg, knn_cells(n2, nseg), g, cell_start, recs, sub, sub_bytes, stream, r, bound, n1,
                          dst_seg_off, nseg, src_seg_off, cell_hint < 0.0f ? (cell_mean_mult >= 0.0f ? cell_mean_mult : KNN_MEAN_MULT) : 0.0f, valid));
     if (valid) (void)hipMemsetAsync(mask, 0, (size_t)n1, stream);  // (the points outside the search get no query: their answer is "no")
-    hipLaunchKernelGGL((k_knn<8, true>), dim3((unsigned)st_div_up(n1, KNN_WAVES)), dim3(KNN_BLOCK), 0, stream, src, n1,
+    hipLaunchKernelGGL((k_knn<8, true>), dim3((unsigned)st_div_up(n1, (int64_t)KNN_WAVES * KNN_QW)), dim3(KNN_BLOCK), 0, stream, src, n1,
                        (const StGrid*)g, (const uint32_t*)cell_start, (const float4*)recs, r, bound, bound_mode,
                        reinterpret_cast<int64_t*>(mask), (float*)nullptr, src_seg_off, nseg, src == dst && n1 == n2 ? 1 : 0, valid);
     ST_CHECK_LAUNCH();

@@ -40,7 +40,10 @@ extern "C" {
  * 113: st_fit_tubes and its size query added (no existing signature changed).
  * 114: st_tree_tally and its size query added (no existing signature changed).
  * 115: st_ground_extent, st_ground_model, st_ground_height and their size query added (no existing signature changed).
- * 116: the neighbour searches serve a run of queries per wavefront (no signature, workspace size or result changed). */
+ * 116: the neighbour searches serve a run of queries per wavefront (no signature, workspace size or result changed).
+ * 117: st_scan_u32_dev and st_fill_u32_len added for the primitive-level tests; st_sort_pairs_u32 ignores the key bits at and
+ * above key_bits (before: it ordered by whole bytes); the coordinate hash probes every slot of a table of up to 4096 slots (no
+ * existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -61,6 +64,12 @@ int64_t st_scan_workspace_bytes(int64_t n);
 int st_scan_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* total, void* ws, int64_t ws_bytes, void* stream);
 int64_t st_sort_workspace_bytes(int64_t n);
 int st_sort_pairs_u32(uint32_t* keys, uint32_t* vals, int64_t n, int key_bits, void* ws, int64_t ws_bytes, void* stream);
+/* the scan over the first min(n, *n_dev) elements (n_dev: device pointer, may be NULL = n); elements past them are neither read
+ * nor written, *total = the sum of the live prefix */
+int st_scan_u32_dev(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* total, void* ws, int64_t ws_bytes, const int64_t* n_dev,
+                    void* stream);
+/* p[0 .. min(n, *n_dev)) = value */
+int st_fill_u32_len(uint32_t* p, int64_t n, const int64_t* n_dev, uint32_t value, void* stream);
 
 /* ---- blocks + voxelisation ------------------------------------------------------------------------
  * replaces: dataset/dataset.py:166-226 (SingleTreeInference.compute_blocks / __getitem__, i.e.

@@ -31,6 +31,8 @@ SIGNATURES = {
     "st_scan_u32": (c_int, [P, P, I64, P, P, I64, P]),
     "st_sort_workspace_bytes": (I64, [I64]),
     "st_sort_pairs_u32": (c_int, [P, P, I64, c_int, P, I64, P]),
+    "st_scan_u32_dev": (c_int, [P, P, I64, P, P, I64, P, P]),
+    "st_fill_u32_len": (c_int, [P, I64, P, ctypes.c_uint32, P]),
     "st_voxelize_workspace_bytes": (I64, [I64, c_int, I64]),
     "st_voxelize_blocks": (c_int, [P, P, I64, c_double, c_double, c_double, c_int, c_int, I64, P, P, P, P, P,
                                    ctypes.POINTER(I64), ctypes.POINTER(I64), P, I64, P]),

@@ -18,7 +18,7 @@ void st_set_error(const char* fmt, ...) {
 extern "C" const char* st_last_error(void) { return g_err; }
 void st_stream_wait(hipStream_t stream) { (void)hipStreamSynchronize(stream); }
 
-extern "C" int st_version(void) { return 116; }
+extern "C" int st_version(void) { return 117; }
 
 // ------------------------------------------------------------------------------------ scan ---
 // 16 items per lane, read as four 16-byte loads where the arrays allow it (the grid builders scan tens of millions of
@@ -171,7 +171,9 @@ void st_fill_u32_dev(uint32_t* p, int64_t n, const int64_t* n_dev, uint32_t valu
 #define SORT_TILE (SORT_BLOCK * SORT_ITEMS)
 #define SORT_WAVES (SORT_BLOCK / 64)
 
-__global__ void __launch_bounds__(SORT_BLOCK) k_sort_hist(const uint32_t* keys, int64_t n, int shift, uint32_t* hist,
+// digit of a pass = (key >> shift) & mask; mask has min(8, key_bits - shift) bits, so the last pass of a key_bits that is no
+// multiple of 8 leaves the bits at and above key_bits out of the order (they travel with their pair)
+__global__ void __launch_bounds__(SORT_BLOCK) k_sort_hist(const uint32_t* keys, int64_t n, int shift, uint32_t mask, uint32_t* hist,
                                                           int64_t nb) {
     __shared__ uint32_t h[256];
     h[threadIdx.x] = 0;
@@ -179,15 +181,15 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_sort_hist(const uint32_t* keys, 
     int64_t base = (int64_t)blockIdx.x * SORT_TILE;
     for (int r = 0; r < SORT_ITEMS; r++) {
         int64_t e = base + (int64_t)r * SORT_BLOCK + threadIdx.x;
-        if (e < n) atomicAdd(&h[(keys[e] >> shift) & 255u], 1u);
+        if (e < n) atomicAdd(&h[(keys[e] >> shift) & mask], 1u);
     }
     __syncthreads();
     hist[(int64_t)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];
 }
 
 __global__ void __launch_bounds__(SORT_BLOCK) k_sort_scatter(const uint32_t* keys, const uint32_t* vals, uint32_t* okeys,
-                                                             uint32_t* ovals, int64_t n, int shift, const uint32_t* hist,
-                                                             int64_t nb) {
+                                                             uint32_t* ovals, int64_t n, int shift, uint32_t mask,
+                                                             const uint32_t* hist, int64_t nb) {
     __shared__ uint32_t running[256];
     __shared__ uint32_t wd[SORT_WAVES][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -200,7 +202,7 @@ __global__ void __launch_bounds__(SORT_BLOCK) k_sort_scatter(const uint32_t* key
         bool valid = e < n;
         uint32_t key = valid ? keys[e] : 0u;
         uint32_t val = valid ? vals[e] : 0u;
-        uint32_t digit = (key >> shift) & 255u;
+        uint32_t digit = (key >> shift) & mask;
         // peers = valid lanes of this wave holding the same digit
         unsigned long long peers = __ballot(valid);
         for (int b = 0; b < 8; b++) {
@@ -256,11 +258,12 @@ int st_radix_sort_pairs_u32(uint32_t* keys, uint32_t* vals, int64_t n, int key_b
     }
     uint32_t *ik = keys, *iv = vals, *ok = tk, *ov = tv;
     for (int shift = 0; shift < key_bits; shift += 8) {
-        hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nb), dim3(SORT_BLOCK), 0, stream, (const uint32_t*)ik, n, shift,
+        const uint32_t mask = key_bits - shift >= 8 ? 255u : (1u << (key_bits - shift)) - 1u;
+        hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nb), dim3(SORT_BLOCK), 0, stream, (const uint32_t*)ik, n, shift, mask,
                            hist, nb);
         ST_TRY(st_exclusive_scan_u32(hist, hist, 256 * nb, nullptr, scan_ws, scan_bytes, stream));
         hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)nb), dim3(SORT_BLOCK), 0, stream, (const uint32_t*)ik,
-                           (const uint32_t*)iv, ok, ov, n, shift, (const uint32_t*)hist, nb);
+                           (const uint32_t*)iv, ok, ov, n, shift, mask, (const uint32_t*)hist, nb);
         uint32_t* t;
         t = ik; ik = ok; ok = t;
         t = iv; iv = ov; ov = t;
@@ -283,6 +286,16 @@ extern "C" int64_t st_sort_workspace_bytes(int64_t n) { return st_sort_ws_bytes(
 extern "C" int st_sort_pairs_u32(uint32_t* keys, uint32_t* vals, int64_t n, int key_bits, void* ws, int64_t ws_bytes,
                                  void* stream) {
     return st_radix_sort_pairs_u32(keys, vals, n, key_bits, ws, ws_bytes, (hipStream_t)stream);
+}
+extern "C" int st_scan_u32_dev(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* total, void* ws, int64_t ws_bytes,
+                               const int64_t* n_dev, void* stream) {
+    return st_exclusive_scan_u32(in, out, n, total, ws, ws_bytes, (hipStream_t)stream, n_dev);
+}
+extern "C" int st_fill_u32_len(uint32_t* p, int64_t n, const int64_t* n_dev, uint32_t value, void* stream) {
+    ST_REQUIRE(n_dev != nullptr, "fill: the device length is required");
+    st_fill_u32_dev(p, n, n_dev, value, (hipStream_t)stream);
+    ST_CHECK_LAUNCH();
+    return ST_OK;
 }
 
 // One query for every workspace size (SURVEY.md section 8b `st_query_workspace`).

@@ -139,9 +139,12 @@ __global__ void __launch_bounds__(RB_BLOCK) k_rb_relabel(const int32_t* out_coor
                                                          unsigned* vals, unsigned long long cap) {
     for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < m; o += (int64_t)gridDim.x * blockDim.x) {
         unsigned long long key = st_pack_key(out_coords[4 * o], out_coords[4 * o + 1], out_coords[4 * o + 2], out_coords[4 * o + 3]);
-        unsigned long long slot = st_hash_slot(key, cap);
-        while (keys[slot] != key) slot = st_hash_next(slot, key, cap);
-        vals[slot] = (unsigned)o;
+        // every emitted row won its key in pass 0, so the key is in the table; the bound is the one of every other probe loop
+        const unsigned long long home = st_hash_slot(key, cap);
+        for (unsigned long long probe = 0; probe < cap && probe < ST_HASH_MAX_PROBE; probe++) {
+            const unsigned long long slot = st_hash_probe(home, key, cap, probe);
+            if (keys[slot] == key) { vals[slot] = (unsigned)o; break; }
+        }
     }
 }
 
@@ -247,7 +250,11 @@ extern "C" int st_build_coord_hash(const int32_t* coords, int64_t n, unsigned lo
     (void)hipMemsetAsync(keys, 0xff, cap * sizeof(unsigned long long), stream);
     (void)hipMemsetAsync(vals, 0xff, cap * sizeof(unsigned), stream);
     if (n > 0) {
-        // capacity >= 2n: an insert can never run out of slots, the flag word is only a guard
+        // No failure report (the flag word is only a guard).  Up to ST_HASH_MAX_PROBE = 4096 slots an insert visits every
+        // slot of the table (st_hash_probe) and capacity >= 2n leaves half of them free: no key can be lost.  In a larger
+        // table an insert stops after 4096 slots -- spread over several lanes up to 8 * 4096 slots, all of its own lane
+        // (an eighth of the table) above that: a loss there takes 4096 occupied slots on one probe sequence at <= 50 % load
+        // (with hashed positions: never seen, never expected), and it would go unreported.
         hipLaunchKernelGGL(k_rb_insert, dim3(rb_grid(n)), dim3(RB_BLOCK), 0, stream, coords, n, keys, vals,
                            (unsigned long long)cap, (unsigned*)nullptr);
     }

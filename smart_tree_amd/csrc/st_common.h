@@ -114,23 +114,39 @@ __device__ __forceinline__ unsigned long long st_hash_next(unsigned long long sl
     const unsigned long long stride = ((st_hash64(key >> 3) >> 29) | 8ull) & ~7ull;  // odd number of groups
     return (slot + stride) & (cap - 1);
 }
+// Slot of probe p (0 = the home slot) of the tables below.  The first cap/8 probes are st_hash_next's walk: the key's own
+// lane in every group, each once (the stride is an odd number of groups).  That walk alone reaches an eighth of the table
+// -- two slots of a table of 16 -- so the sequence goes on: the same walk through the next lane ((lane + 1) & 7), then the
+// one after, and after cap probes every slot of the table has been visited exactly once.  At the load the callers size
+// for a sequence ends long before it leaves its lane, so the cache lines touched are the ones of the lane walk.
+__device__ __forceinline__ unsigned long long st_hash_probe(unsigned long long home, unsigned long long key, unsigned long long cap,
+                                                            unsigned long long p) {
+    const unsigned long long stride = ((st_hash64(key >> 3) >> 29) | 8ull) & ~7ull;
+    const unsigned long long groups = cap >> 3;
+    if (p < groups) return (home + p * stride) & (cap - 1);
+    const unsigned long long turn = p >> __popcll(groups - 1), at = (home + (p & (groups - 1)) * stride) & (cap - 1);
+    return (at & ~7ull) | ((at + turn) & 7ull);
+}
 
-// Open-addressing table: keys[cap] (u64), vals[cap] (u32).  cap is a power of two (>= 8).
+// Open-addressing table: keys[cap] (u64), vals[cap] (u32).  cap is a power of two (>= 16).
 // insert-with-min: the smallest value ever offered for a key wins (deterministic).
 // An insert gives up (returns false = "table full", the caller flags it and the host retries with a larger table) after
 // ST_HASH_MAX_PROBE slots: below the 50 % load the callers size for, probe sequences are a handful of slots long, and
 // without the limit every insert into a table that did fill up would walk ALL of it.
+// What an insert can reach: every slot of a table of up to ST_HASH_MAX_PROBE slots (there it fails only when the table IS
+// full); ST_HASH_MAX_PROBE slots spread over the first lanes of its sequence in a table of up to 8 * ST_HASH_MAX_PROBE
+// slots; above that, ST_HASH_MAX_PROBE slots of its own lane only.
 #define ST_HASH_MAX_PROBE 4096ull
 __device__ __forceinline__ bool st_hash_insert_min(unsigned long long* keys, unsigned* vals, unsigned long long cap,
                                                    unsigned long long key, unsigned val) {
-    unsigned long long slot = st_hash_slot(key, cap);
+    const unsigned long long home = st_hash_slot(key, cap);
     for (unsigned long long probe = 0; probe < cap && probe < ST_HASH_MAX_PROBE; probe++) {
+        const unsigned long long slot = st_hash_probe(home, key, cap, probe);
         unsigned long long prev = atomicCAS(&keys[slot], (unsigned long long)ST_EMPTY_KEY, key);
         if (prev == ST_EMPTY_KEY || prev == key) {
             atomicMin(&vals[slot], val);
             return true;
         }
-        slot = st_hash_next(slot, key, cap);
     }
     return false;
 }
@@ -142,28 +158,28 @@ __device__ __forceinline__ bool st_hash_insert_min(unsigned long long* keys, uns
 __device__ __forceinline__ bool st_hash_insert_min_dup(unsigned long long* keys, unsigned* vals, unsigned long long cap,
                                                        unsigned long long key, unsigned val, const unsigned* give_up = nullptr,
                                                        unsigned give_up_bit = 0u) {
-    unsigned long long slot = st_hash_slot(key, cap);
+    const unsigned long long home = st_hash_slot(key, cap);
     for (unsigned long long probe = 0; probe < cap && probe < ST_HASH_MAX_PROBE; probe++) {
         if (give_up && (probe & 63ull) == 63ull &&
             (__hip_atomic_load(give_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & give_up_bit)) return false;
+        const unsigned long long slot = st_hash_probe(home, key, cap, probe);
         unsigned long long prev = keys[slot];
         if (prev == ST_EMPTY_KEY) prev = atomicCAS(&keys[slot], (unsigned long long)ST_EMPTY_KEY, key);
         if (prev == ST_EMPTY_KEY || prev == key) {
             if (vals[slot] > val) atomicMin(&vals[slot], val);
             return true;
         }
-        slot = st_hash_next(slot, key, cap);
     }
     return false;
 }
 __device__ __forceinline__ int st_hash_find(const unsigned long long* keys, const unsigned* vals, unsigned long long cap,
                                             unsigned long long key) {
-    unsigned long long slot = st_hash_slot(key, cap);
+    const unsigned long long home = st_hash_slot(key, cap);
     for (unsigned long long probe = 0; probe < cap && probe < ST_HASH_MAX_PROBE; probe++) {
+        const unsigned long long slot = st_hash_probe(home, key, cap, probe);
         unsigned long long k = keys[slot];
         if (k == key) return (int)vals[slot];
         if (k == ST_EMPTY_KEY) return -1;
-        slot = st_hash_next(slot, key, cap);
     }
     return -1;
 }
@@ -184,8 +200,9 @@ __device__ __forceinline__ void st_hash_find_batch(const unsigned long long* key
     for (int j = 0; j < N; j++) {
         if (got[j] != key[j] && got[j] != ST_EMPTY_KEY) {  // displaced: follow the probe sequence
             unsigned long long s = slot[j], g = got[j];
+            const unsigned long long home = slot[j];
             for (unsigned long long probe = 1; probe < cap && probe < ST_HASH_MAX_PROBE && g != key[j] && g != ST_EMPTY_KEY; probe++) {
-                s = st_hash_next(s, key[j], cap);
+                s = st_hash_probe(home, key[j], cap, probe);
                 g = keys[s];
             }
             slot[j] = s;
@@ -232,6 +249,7 @@ int st_exclusive_scan_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t
                           hipStream_t stream, const int64_t* n_dev = nullptr);
 void st_fill_u32_dev(uint32_t* p, int64_t n, const int64_t* n_dev, uint32_t value, hipStream_t stream);
 int64_t st_sort_ws_bytes(int64_t n);
-// Stable LSD radix sort of (key, val) pairs on key bits [0, key_bits).  Result lands in keys/vals.
+// Stable LSD radix sort of (key, val) pairs on key bits [0, key_bits): the bits at and above key_bits travel with their pair and
+// take no part in the order (the last pass masks its digit).  Result lands in keys/vals.
 int st_radix_sort_pairs_u32(uint32_t* keys, uint32_t* vals, int64_t n, int key_bits, void* ws, int64_t ws_bytes,
                             hipStream_t stream);

@@ -61,6 +61,28 @@ def apply_overrides(cfg: dict, overrides=()) -> dict:
     return cfg
 
 
+def cloud_command(argv, defaults: dict, usage: str):
+    """The opening of the `key=value` commands that work on a cloud and its skeleton (`segmentation`, `refine`, `inventory`):
+    (cfg, device, cloud).  `defaults` with the overrides applied; a key it does not hold, or no `cloud`, `skeleton` or `out`, ends
+    with `usage`; the cloud is loaded onto `cfg["device"]` and, with `centre=true`, centred by `CentreCloud`."""
+    import sys
+
+    import torch
+
+    from .util.file import load_cloud
+
+    cfg = apply_overrides(dict(defaults), argv if argv is not None else sys.argv[1:])
+    unknown = sorted(set(cfg) - set(defaults))
+    if unknown or cfg["cloud"] is None or cfg["skeleton"] is None or cfg["out"] is None:
+        raise SystemExit(usage + (f"  (unknown: {', '.join(unknown)})" if unknown else ""))
+    dev = torch.device(cfg["device"])
+    cloud = load_cloud(cfg["cloud"]).to_device(dev)
+    if str(cfg["centre"]).lower() in ("true", "1", "yes", "on"):
+        from .dataset.augmentations import CentreCloud
+        cloud = CentreCloud()(cloud)
+    return cfg, dev, cloud
+
+
 def resolve(cfg: dict) -> dict:
     now = time.localtime()
     done: dict = {}

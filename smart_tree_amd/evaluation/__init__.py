@@ -18,7 +18,7 @@ import math
 import numpy as np
 import torch
 
-from ..data_types.tree import DisjointTreeSkeleton, TreeSkeleton
+from ..data_types.flat import FlatSkeletons
 from ..data_types.tube import sample_tubes_device
 from .prediction import PredictionTally, derive_metrics, prediction_tally, segment_offsets  # noqa: F401  (per-point predictions)
 
@@ -26,48 +26,20 @@ DEFAULT_THRESHOLDS = tuple(round(0.1 * k, 1) for k in range(1, 11))
 MAX_THRESHOLDS = 32
 
 
-def _branch_tubes(branches):
-    branches = [b for b in branches if len(b) >= 2]
-    if not branches:
-        z = torch.zeros((0, 3), dtype=torch.float32)
-        return z, z.clone(), z[:, 0].clone(), z[:, 0].clone()
-    cat = lambda parts: torch.cat([torch.as_tensor(p).detach().cpu().float() for p in parts])
-    return (cat([b.xyz[:-1] for b in branches]), cat([b.xyz[1:] for b in branches]),
-            cat([b.radii.reshape(-1)[:-1] for b in branches]), cat([b.radii.reshape(-1)[1:] for b in branches]))
-
-
 def skeleton_tubes(skeleton):
     """(a [M,3], b [M,3], r1 [M], r2 [M]) float32 host tensors in `to_tubes()` order, for a `TreeSkeleton`, a
     `DisjointTreeSkeleton`, or the flat arrays `save_skeleton_npz` writes (a mapping with `branches` [B,5] = tree, id,
-    parent, offset, length; `xyz` [P,3]; `radii` [P])."""
-    if isinstance(skeleton, TreeSkeleton):
-        return _branch_tubes(skeleton.branches.values())
-    if isinstance(skeleton, DisjointTreeSkeleton):
-        return _branch_tubes([b for s in skeleton.skeletons for b in s.branches.values()])
-    try:
-        rows, xyz, radii = skeleton["branches"], skeleton["xyz"], skeleton["radii"]
-    except (KeyError, TypeError, IndexError):
-        raise TypeError(f"skeleton_tubes: a TreeSkeleton, a DisjointTreeSkeleton or flat branches / xyz / radii arrays, got {type(skeleton).__name__}")
-    rows = np.asarray(rows, dtype=np.int64).reshape(-1, 5)
-    xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
-    radii = np.asarray(radii, dtype=np.float32).reshape(-1)
-    start = np.concatenate([np.arange(o, o + n - 1) for o, n in zip(rows[:, 3], rows[:, 4])] or [np.zeros(0, np.int64)]).astype(np.int64)
-    t = lambda x: torch.from_numpy(np.ascontiguousarray(x))
-    return t(xyz[start]), t(xyz[start + 1]), t(radii[start]), t(radii[start + 1])
+    parent, offset, length; `xyz` [P,3]; `radii` [P]): `FlatSkeletons.tubes` of the one skeleton."""
+    flat = FlatSkeletons([skeleton], "skeleton_tubes")
+    return tuple(torch.from_numpy(t) for t in flat.tubes(*flat.float32()))
 
 
 def skeleton_owners(skeleton) -> np.ndarray:
     """int64 [B,4]: (tree, branch id, parent id, number of tubes) of every branch, in `skeleton_tubes` order -- the tubes of a
     branch are contiguous, so the rows say who owns each tube.  `tree` is the tree's index in a `DisjointTreeSkeleton`, 0 for a
     `TreeSkeleton`, the file's tree column for flat arrays; a branch of fewer than two points has no tube."""
-    if isinstance(skeleton, TreeSkeleton):
-        rows = [(0, k, br.parent_id, max(len(br) - 1, 0)) for k, br in skeleton.branches.items()]
-    elif isinstance(skeleton, DisjointTreeSkeleton):
-        rows = [(t, k, br.parent_id, max(len(br) - 1, 0)) for t, s in enumerate(skeleton.skeletons) for k, br in s.branches.items()]
-    else:
-        flat = np.asarray(skeleton["branches"], dtype=np.int64).reshape(-1, 5)
-        rows = [(int(r[0]), int(r[1]), int(r[2]), max(int(r[4]) - 1, 0)) for r in flat]
-    return np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+    flat = FlatSkeletons([skeleton], "skeleton_owners")
+    return np.column_stack([flat.rows[:, 1:4], flat.tubes_of_row])
 
 
 def branch_key(tree, branch):

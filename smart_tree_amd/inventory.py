@@ -18,7 +18,6 @@ occupied cells, not a hull; `measure_trees` takes the classes 0..254 of `cloud.c
 from __future__ import annotations
 
 import json
-import sys
 from dataclasses import dataclass, field
 from pathlib import Path
 
@@ -27,7 +26,7 @@ import torch
 
 from . import _lib
 from .data_types.cloud import Cloud
-from .data_types.tree import DisjointTreeSkeleton, TreeSkeleton
+from .data_types.flat import FlatSkeletons, points_and_skeletons
 
 TALLY_OUTPUTS = ("box", "counts", "area_cells", "profile")
 MAX_CLASSES = 255
@@ -74,56 +73,20 @@ def tree_tally(pts, tree, n_trees, cls=None, n_classes=1, up=1, cell=0.1, layers
 
 
 # ------------------------------------------------------------------------------------------------ the skeleton, flat ---
-def _branches_of(skeleton):
-    """[(tree, branch id, parent id, xyz [n,3], radii [n])] in `evaluation.skeleton_owners` order, float64."""
-    h = lambda t: torch.as_tensor(t).detach().cpu().double().numpy()
-    if isinstance(skeleton, TreeSkeleton):
-        return [(0, int(k), int(b.parent_id), h(b.xyz).reshape(-1, 3), h(b.radii).reshape(-1)) for k, b in skeleton.branches.items()]
-    if isinstance(skeleton, DisjointTreeSkeleton):
-        return [(t, int(k), int(b.parent_id), h(b.xyz).reshape(-1, 3), h(b.radii).reshape(-1))
-                for t, s in enumerate(skeleton.skeletons) for k, b in s.branches.items()]
-    try:
-        rows, xyz, radii = skeleton["branches"], skeleton["xyz"], skeleton["radii"]
-    except (KeyError, TypeError, IndexError):
-        raise TypeError(f"measure_trees: a TreeSkeleton, a DisjointTreeSkeleton or flat branches / xyz / radii arrays, got {type(skeleton).__name__}")
-    rows = np.asarray(rows, np.int64).reshape(-1, 5)
-    xyz, radii = np.asarray(xyz, np.float64).reshape(-1, 3), np.asarray(radii, np.float64).reshape(-1)
-    return [(int(t), int(b), int(p), xyz[o:o + n], radii[o:o + n]) for t, b, p, o, n in rows.tolist()]
-
-
-class _Flat:
-    """The skeletons of a call: `rows` int64 [B,6] = cloud, tree, branch id, parent id, vertex offset, vertices; `xyz` [P,3],
-    `radii` [P] float64; `tree_rows` int64 [T,2] = (cloud, tree) in the order of their first branch; `tree_of_branch` [B]."""
-
-    def __init__(self, skeletons):
-        rows, xyz, radii, off = [], [np.zeros((0, 3))], [np.zeros(0)], 0
-        for c, sk in enumerate(skeletons):
-            for tree, bid, parent, bx, br in _branches_of(sk):
-                rows.append((c, tree, bid, parent, off, len(bx)))
-                xyz.append(bx)
-                radii.append(br)
-                off += len(bx)
-        self.rows = np.asarray(rows, np.int64).reshape(-1, 6)
-        self.xyz, self.radii = np.concatenate(xyz), np.concatenate(radii)
-        seen = {}
-        self.tree_of_branch = np.asarray([seen.setdefault((c, t), len(seen)) for c, t in self.rows[:, :2].tolist()], np.int64)
-        self.tree_rows = np.asarray(list(seen), np.int64).reshape(-1, 2)
-        self.n_clouds = len(skeletons)
-
-    def lookup(self):
-        """(table int32 [S + 1], base int64 [clouds], span int64 [clouds]): table[base[c] + t] is the row of tree t of cloud c among
-        `tree_rows` for 0 <= t < span[c], -1 for a tree id the skeleton does not hold; the last entry (-1) is what a point without a
-        tree indexes."""
-        if len(self.tree_rows) and (self.tree_rows[:, 1].min() < 0 or self.tree_rows[:, 1].max() >= 1 << 24):
-            raise ValueError("measure_trees: tree ids must be in [0, 2^24)")
-        span = np.zeros(self.n_clouds, np.int64)
-        for c, t in self.tree_rows.tolist():
-            span[c] = max(span[c], t + 1)
-        base = np.concatenate([[0], np.cumsum(span)]).astype(np.int64)
-        table = np.full(int(base[-1]) + 1, -1, np.int32)
-        for row, (c, t) in enumerate(self.tree_rows.tolist()):
-            table[base[c] + t] = row
-        return table, base[:-1], span
+def tree_lookup(flat: FlatSkeletons):
+    """(table int32 [S + 1], base int64 [clouds], span int64 [clouds]): table[base[c] + t] is the row of tree t of cloud c among
+    `flat.tree_rows` for 0 <= t < span[c], -1 for a tree id the skeleton does not hold; the last entry (-1) is what a point without
+    a tree indexes."""
+    if len(flat.tree_rows) and (flat.tree_rows[:, 1].min() < 0 or flat.tree_rows[:, 1].max() >= 1 << 24):
+        raise ValueError("measure_trees: tree ids must be in [0, 2^24)")
+    span = np.zeros(flat.n_clouds, np.int64)
+    for c, t in flat.tree_rows.tolist():
+        span[c] = max(span[c], t + 1)
+    base = np.concatenate([[0], np.cumsum(span)]).astype(np.int64)
+    table = np.full(int(base[-1]) + 1, -1, np.int32)
+    for row, (c, t) in enumerate(flat.tree_rows.tolist()):
+        table[base[c] + t] = row
+    return table, base[:-1], span
 
 
 # ------------------------------------------------------------------------------------------------ host metrics ---
@@ -138,7 +101,7 @@ def _segment_distance2(p, a, b):
     return (v * v).sum(1)
 
 
-def branch_table(flat: _Flat, points=None):
+def branch_table(flat: FlatSkeletons, points=None):
     """(float64 [B,14], BRANCH_COLUMNS; orphans int64 [k,3] = cloud, tree, branch) of the skeletons in `flat`.
     order: a root is 0, a child its parent's plus 1; a branch whose parent is not in its tree counts as a root (and is an orphan when
     it names one: a parent id other than -1 and its own).  volume = sum pi h (r1^2 + r1 r2 + r2^2) / 3 and area = sum
@@ -151,9 +114,8 @@ def branch_table(flat: _Flat, points=None):
     if not B:
         return out, np.zeros((0, 3), np.int64)
     out[:, :4] = rows[:, :4]
-    tubes = np.maximum(rows[:, 5] - 1, 0)
+    tubes, start, first_tube = flat.tubes_of_row, flat.tube_start, flat.tube_first
     out[:, 5] = tubes
-    start = np.concatenate([np.arange(o, o + n - 1) for o, n in rows[:, 4:6].tolist() if n >= 2] or [np.zeros(0, np.int64)]).astype(np.int64)
     owner = np.repeat(np.arange(B), tubes)
     d = xyz[start + 1] - xyz[start]
     h = np.sqrt((d * d).sum(1))
@@ -186,7 +148,6 @@ def branch_table(flat: _Flat, points=None):
             order[j] = depth
             depth += 1
     out[:, 4] = order
-    first_tube = np.concatenate([[0], np.cumsum(tubes)])
     for k in range(B):
         j = int(parent_row[k])
         if j < 0 or tubes[k] < 1 or tubes[j] < 1:
@@ -216,7 +177,7 @@ def tree_columns(n_classes: int) -> tuple:
     return TREE_HEAD + tuple(f"points_class_{k}" for k in range(n_classes)) + TREE_TAIL
 
 
-def tree_table(flat: _Flat, branches, box, counts, area_cells, profile, cell, breast_height=1.3, up=1, ground_base=None):
+def tree_table(flat: FlatSkeletons, branches, box, counts, area_cells, profile, cell, breast_height=1.3, up=1, ground_base=None):
     """float64 [T, 3 + C + 17] (`tree_columns(C)`) from the tallies (host arrays) and the branch table.  `ground_base` [T] (or None):
     the terrain under every tree's root; where it is finite it is the tree's base instead of its lowest point."""
     T, C = len(flat.tree_rows), counts.shape[1]
@@ -342,11 +303,11 @@ def _used_classes(counts) -> int:
     return int(used[-1]) + 1 if len(used) else 1
 
 
-def point_rows(flat: _Flat, tree_id, seg_off=None, device=None) -> torch.Tensor:
+def point_rows(flat: FlatSkeletons, tree_id, seg_off=None, device=None) -> torch.Tensor:
     """int32 [n] on the device: the row among `flat.tree_rows` of every point's tree, from the segmentation's `tree_id` (the tree's
     id inside its cloud) and the cloud's tree offset; -1 for a point without a tree.  Nothing is read back."""
     dev = torch.device(device) if device is not None else tree_id.device
-    table, base, span = flat.lookup()
+    table, base, span = tree_lookup(flat)
     tree_id = tree_id.to(dev).long().reshape(-1)
     n = tree_id.shape[0]
     if seg_off is not None:
@@ -360,7 +321,7 @@ def point_rows(flat: _Flat, tree_id, seg_off=None, device=None) -> torch.Tensor:
     return torch.from_numpy(table).to(dev).index_select(0, slot)
 
 
-def root_positions(flat: _Flat, branches) -> np.ndarray:
+def root_positions(flat: FlatSkeletons, branches) -> np.ndarray:
     """float64 [T,3]: the first vertex of every tree's root branch (the first of order 0), NaN for a tree without one."""
     out = np.full((len(flat.tree_rows), 3), np.nan)
     for r in range(len(flat.tree_rows)):
@@ -382,24 +343,16 @@ def measure_trees(cloud, skeleton, segmentation=None, cell=0.1, layers=256, brea
     (NaN) the base stays the tree's lowest point.  None changes nothing."""
     from .segmentation import segment_cloud
 
-    if isinstance(cloud, Cloud):
-        xyz, seg_off, class_l = cloud.xyz, cloud.seg_off, cloud.class_l
-    else:
-        xyz, seg_off, class_l = torch.as_tensor(np.asarray(cloud) if not torch.is_tensor(cloud) else cloud), None, None
-    dev = torch.device(device) if device is not None else xyz.device
-    pts = xyz.to(dev).float().reshape(-1, 3).contiguous()
-    n = pts.shape[0]
-    skeletons = list(skeleton) if isinstance(skeleton, (list, tuple)) else [skeleton]
-    n_clouds = 1 if seg_off is None else int(seg_off.shape[0]) - 1
-    if len(skeletons) != n_clouds:
-        raise ValueError(f"measure_trees: {len(skeletons)} skeleton(s) for {n_clouds} cloud(s); a collated Cloud takes a list, one per cloud")
+    pts, seg_off, skeletons, _, n_clouds = points_and_skeletons(cloud, skeleton, device, "measure_trees")
+    dev, n = pts.device, pts.shape[0]
+    class_l = cloud.class_l if isinstance(cloud, Cloud) else None
     if not (up in (0, 1, 2) and cell > 0 and np.isfinite(cell) and 1 <= int(layers) <= 4096):
         raise ValueError(f"measure_trees: up in 0..2, cell > 0 and 1 <= layers <= 4096 (got {up}, {cell}, {layers})")
     if segmentation is None:
         segmentation = segment_cloud(Cloud(xyz=pts, seg_off=seg_off) if seg_off is not None else pts, skeleton, max_distance=max_distance, device=dev)
     if len(segmentation) != n:
         raise ValueError(f"measure_trees: a segmentation of {len(segmentation)} points for a cloud of {n}")
-    flat = _Flat(skeletons)
+    flat = FlatSkeletons(skeletons, "measure_trees")
     if len(flat.rows) != len(segmentation.branches):
         raise ValueError(f"measure_trees: a segmentation onto {len(segmentation.branches)} branches for a skeleton of {len(flat.rows)}")
     T = len(flat.tree_rows)
@@ -447,23 +400,15 @@ def summary(inv: TreeInventory) -> str:
 # ---------------------------------------------------------------------------------------------------------------- cli ---
 DEFAULTS = {"cloud": None, "skeleton": None, "out": None, "cell": 0.1, "layers": 256, "breast_height": 1.3, "max_distance": None,
             "centre": False, "device": "cuda:0"}
+USAGE = ("usage: python -m smart_tree_amd.inventory cloud=<.npz|.ply> skeleton=<skeleton.npz> out=<dir> [cell=0.1] [layers=256] "
+         "[breast_height=1.3] [max_distance=] [centre=false] [device=]")
 
 
 def main(argv=None) -> TreeInventory:
-    from .config import apply_overrides
+    from .config import cloud_command
     from .evaluate import load_any_skeleton
-    from .util.file import load_cloud
 
-    cfg = apply_overrides(dict(DEFAULTS), argv if argv is not None else sys.argv[1:])
-    unknown = sorted(set(cfg) - set(DEFAULTS))
-    if unknown or cfg["cloud"] is None or cfg["skeleton"] is None or cfg["out"] is None:
-        raise SystemExit("usage: python -m smart_tree_amd.inventory cloud=<.npz|.ply> skeleton=<skeleton.npz> out=<dir> [cell=0.1] [layers=256] "
-                         "[breast_height=1.3] [max_distance=] [centre=false] [device=]" + (f"  (unknown: {', '.join(unknown)})" if unknown else ""))
-    dev = torch.device(cfg["device"])
-    cloud = load_cloud(cfg["cloud"]).to_device(dev)
-    if str(cfg["centre"]).lower() in ("true", "1", "yes", "on"):
-        from .dataset.augmentations import CentreCloud
-        cloud = CentreCloud()(cloud)
+    cfg, dev, cloud = cloud_command(argv, DEFAULTS, USAGE)
     inv = measure_trees(cloud, load_any_skeleton(cfg["skeleton"]), cell=float(cfg["cell"]), layers=int(cfg["layers"]),
                         breast_height=float(cfg["breast_height"]),
                         max_distance=None if cfg["max_distance"] is None else float(cfg["max_distance"]), device=dev)

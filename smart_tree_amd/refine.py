@@ -19,18 +19,15 @@ there is no taper or monotonicity constraint along a branch.
 """
 from __future__ import annotations
 
-import sys
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Optional
+from typing import NamedTuple
 
 import numpy as np
 import torch
 
 from . import _lib
-from .data_types.branch import BranchSkeleton
-from .data_types.cloud import Cloud
-from .data_types.tree import DisjointTreeSkeleton, TreeSkeleton
+from .data_types.flat import FlatSkeletons, points_and_skeletons
 
 FIT_COLUMNS = ("points", "radius", "offset_x", "offset_y", "offset_z", "rms", "spread", "status")
 BRANCH_COLUMNS = ("cloud", "tree", "branch", "parent", "tubes", "fitted_tubes", "points", "mean_rms", "mean_radius_change")
@@ -62,96 +59,35 @@ def fit_tubes(pts, tube, a, b, r1, r2, max_relative=0.5, min_points=8, min_sprea
 
 
 # ------------------------------------------------------------------------------------------------ host side ---
-class _Flat:
-    """The skeletons of a call as flat host arrays: `rows` int64 [B,6] = cloud, tree (index in its cloud), branch id, parent id,
-    offset, length; `xyz` [P,3], `radii` [P] float32; `trees`: per cloud the (tree id, branch records) the result is rebuilt from."""
-
-    def __init__(self, skeletons):
-        rows, xyz, radii, self.trees, off = [], [], [], [], 0
-        for c, sk in enumerate(skeletons):
-            cloud_trees = []
-            for t, (tree_id, branches) in enumerate(_trees_of(sk)):
-                recs = []
-                for bid, parent, child, bx, br, column in branches:
-                    rows.append((c, t, bid, parent, off, len(bx)))
-                    xyz.append(bx)
-                    radii.append(br)
-                    recs.append((bid, parent, child, off, len(bx), column))
-                    off += len(bx)
-                cloud_trees.append((tree_id, recs))
-            self.trees.append(cloud_trees)
-        self.rows = np.asarray(rows, np.int64).reshape(-1, 6)
-        self.xyz = np.concatenate(xyz).astype(np.float32).reshape(-1, 3) if xyz else np.zeros((0, 3), np.float32)
-        self.radii = np.concatenate(radii).astype(np.float32).reshape(-1) if radii else np.zeros(0, np.float32)
-        P = len(self.xyz)
-        # vertex i of a branch touches its tubes i - 1 and i (the tubes of a branch are contiguous in `to_tubes()` order)
-        self.lo, self.hi = np.full(P, -1, np.int64), np.full(P, -1, np.int64)
-        self.pinned = np.zeros(P, bool)  # the first vertex of a branch with a parent: the connection point `repair` put on the parent's axis
-        start, tube_off, t = [], [0], 0
-        known = {(int(r[0]), int(r[1]), int(r[2])) for r in self.rows}
-        for k, (c, tr, bid, parent, o, n) in enumerate(self.rows.tolist()):
-            while len(tube_off) <= c:
-                tube_off.append(t)
-            if n >= 2:
-                ids = np.arange(t, t + n - 1)
-                self.hi[o:o + n - 1], self.lo[o + 1:o + n] = ids, ids
-                start.append(np.arange(o, o + n - 1))
-                t += n - 1
-            if n and parent != bid and (c, tr, parent) in known:
-                self.pinned[o] = True
-        while len(tube_off) <= len(skeletons):
-            tube_off.append(t)
-        self.start = np.concatenate(start).astype(np.int64) if start else np.zeros(0, np.int64)
-        self.tube_off = np.asarray(tube_off, np.int64)
-        self.tubes_of_row = np.maximum(self.rows[:, 5] - 1, 0) if len(self.rows) else np.zeros(0, np.int64)
-
-    def tubes(self, xyz, radii):
-        return xyz[self.start], xyz[self.start + 1], radii[self.start], radii[self.start + 1]
-
-    def rebuild(self, xyz, radii) -> list:
-        out = []
-        for cloud_trees in self.trees:
-            trees = []
-            for tree_id, recs in cloud_trees:
-                branches = {}
-                for bid, parent, child, o, n, column in recs:
-                    br = BranchSkeleton(bid, parent, torch.from_numpy(xyz[o:o + n].copy()), torch.from_numpy(radii[o:o + n].copy()).reshape(-1, 1), child)
-                    if not column:  # `smooth` leaves the radii of the branches it touched as [n]: the refined branch keeps the input's shape
-                        br.radii = br.radii.reshape(-1)
-                    branches[bid] = br
-                trees.append(TreeSkeleton(tree_id, branches))
-            out.append(DisjointTreeSkeleton(trees))
-        return out
+class VertexLinks(NamedTuple):
+    """Per vertex of a `FlatSkeletons`: the tubes it ends (`lo`) and begins (`hi`), -1 for none -- vertex i of a branch touches its
+    tubes i - 1 and i -- and `pinned`: the first vertex of a branch with a parent, the connection point `repair` put on the
+    parent's axis."""
+    lo: np.ndarray
+    hi: np.ndarray
+    pinned: np.ndarray
 
 
-def _trees_of(skeleton):
-    """[(tree id, [(branch id, parent id, child id, xyz [n,3], radii [n], radii were [n,1])])] of any skeleton kind `segment_cloud` takes."""
-    h = lambda t: torch.as_tensor(t).detach().cpu().float().numpy()
-    if isinstance(skeleton, TreeSkeleton):
-        skeleton = DisjointTreeSkeleton([skeleton])
-    if isinstance(skeleton, DisjointTreeSkeleton):
-        return [(s._id, [(b._id, b.parent_id, b.child_id, h(b.xyz).reshape(-1, 3), h(b.radii).reshape(-1), torch.as_tensor(b.radii).ndim == 2)
-                         for b in s.branches.values()]) for s in skeleton.skeletons]
-    try:
-        rows, xyz, radii = skeleton["branches"], skeleton["xyz"], skeleton["radii"]
-    except (KeyError, TypeError, IndexError):
-        raise TypeError(f"refine_skeleton: a TreeSkeleton, a DisjointTreeSkeleton or flat branches / xyz / radii arrays, got {type(skeleton).__name__}")
-    rows = np.asarray(rows, np.int64).reshape(-1, 5)
-    xyz, radii = np.asarray(xyz, np.float32).reshape(-1, 3), np.asarray(radii, np.float32).reshape(-1)
-    trees = {}
-    for tree, bid, parent, o, n in rows.tolist():  # the trees in the order of their first branch
-        trees.setdefault(tree, []).append((bid, parent, None, xyz[o:o + n], radii[o:o + n], True))
-    return list(trees.items())
+def vertex_links(flat: FlatSkeletons) -> VertexLinks:
+    P, tube = len(flat.xyz), np.arange(len(flat.tube_start))
+    lo, hi, pinned = np.full(P, -1, np.int64), np.full(P, -1, np.int64), np.zeros(P, bool)
+    hi[flat.tube_start], lo[flat.tube_start + 1] = tube, tube
+    rows = flat.rows.tolist()
+    known = {(c, tr, bid) for c, tr, bid, _, _, _ in rows}
+    for c, tr, bid, parent, o, n in rows:
+        if n and parent != bid and (c, tr, parent) in known:
+            pinned[o] = True
+    return VertexLinks(lo, hi, pinned)
 
 
-def update_vertices(flat: _Flat, xyz, radii, xyz0, radii0, fit, max_ratio=2.0, move_axis=True):
+def update_vertices(links: VertexLinks, xyz, radii, xyz0, radii0, fit, max_ratio=2.0, move_axis=True):
     """One vertex update from a per-tube table `fit` [m,8]: (new xyz, new radii) float32.  A vertex's radius becomes the N-weighted mean
     of R over its (at most two) tubes with status >= 1, kept within [prior / max_ratio, prior * max_ratio]; its position moves by the
     N-weighted mean offset over those with status 2 and stays within one prior radius of the prior position; the prior is the input
     skeleton (xyz0, radii0).  Without a fitted tube a vertex keeps both; a pinned vertex keeps its position."""
     pad = np.concatenate([np.asarray(fit, np.float64).reshape(-1, 8), np.zeros((1, 8))])  # the last row is what "no tube" (-1) indexes
     n_r, n_m = pad[:, 0] * (pad[:, 7] >= 1), pad[:, 0] * (pad[:, 7] == 2)
-    lo, hi = flat.lo, flat.hi
+    lo, hi = links.lo, links.hi
     r0 = radii0.astype(np.float64)
     new_r, new_x = radii.astype(np.float64), xyz.astype(np.float64)
     w = n_r[lo] + n_r[hi]
@@ -167,7 +103,7 @@ def update_vertices(flat: _Flat, xyz, radii, xyz0, radii0, fit, max_ratio=2.0, m
             d = new_x + move - xyz0.astype(np.float64)  # from the prior position
             far = np.sqrt((d * d).sum(1))
             d = np.where((far > r0)[:, None], d * (r0 / far)[:, None], d)
-        ok = (w > 0) & (r0 > 0) & ~flat.pinned & np.isfinite(d).all(1)
+        ok = (w > 0) & (r0 > 0) & ~links.pinned & np.isfinite(d).all(1)
         new_x = np.where(ok[:, None], xyz0.astype(np.float64) + d, new_x)
     return new_x.astype(np.float32), new_r.astype(np.float32)
 
@@ -204,7 +140,7 @@ class SkeletonFit:
             return SkeletonFit(z["tubes"], z["branches"], z["tube_off"], int(z["iterations"]))
 
 
-def _branch_table(flat: _Flat, fit, radii0, radii) -> np.ndarray:
+def _branch_table(flat: FlatSkeletons, fit, radii0, radii) -> np.ndarray:
     rows = flat.rows
     out = np.full((len(rows), 9), np.nan)
     if not len(rows):
@@ -234,36 +170,28 @@ def refine_skeleton(cloud_or_xyz, skeleton, iterations=2, max_distance=None, max
     (`DisjointTreeSkeleton` or a list of them -- same ids, parents and vertex counts; the input is not modified --, `SkeletonFit`)."""
     from .segmentation import segment_points
 
-    if isinstance(cloud_or_xyz, Cloud):
-        xyz, seg_off = cloud_or_xyz.xyz, cloud_or_xyz.seg_off
-    else:
-        xyz, seg_off = torch.as_tensor(np.asarray(cloud_or_xyz) if not torch.is_tensor(cloud_or_xyz) else cloud_or_xyz), None
-    dev = torch.device(device) if device is not None else xyz.device
-    pts = xyz.to(dev).float().reshape(-1, 3).contiguous()
-    many = isinstance(skeleton, (list, tuple))
-    skeletons = list(skeleton) if many else [skeleton]
-    n_clouds = 1 if seg_off is None else int(seg_off.shape[0]) - 1
-    if len(skeletons) != n_clouds:
-        raise ValueError(f"refine_skeleton: {len(skeletons)} skeleton(s) for {n_clouds} cloud(s); a collated Cloud takes a list, one per cloud")
+    pts, seg_off, skeletons, many, _ = points_and_skeletons(cloud_or_xyz, skeleton, device, "refine_skeleton")
+    dev = pts.device
     if int(iterations) < 0:
         raise ValueError(f"refine_skeleton: iterations must be >= 0, got {iterations}")
     if not max_ratio >= 1.0:
         raise ValueError(f"refine_skeleton: max_ratio must be >= 1, got {max_ratio}")
-    flat = _Flat(skeletons)
+    flat = FlatSkeletons(skeletons, "refine_skeleton")
+    links = vertex_links(flat)
     batched = seg_off is not None
     pt_off = seg_off if batched else None
     tube_off = torch.from_numpy(flat.tube_off.astype(np.int32)) if batched else None
-    xyz0, radii0 = flat.xyz, flat.radii
+    xyz0, radii0 = flat.float32()
     cur_xyz, cur_r = xyz0.copy(), radii0.copy()
-    m = len(flat.start)
+    m = len(flat.tube_start)
     fit = np.zeros((m, 8))
     for _ in range(int(iterations)):
         a, b, r1, r2 = (torch.from_numpy(np.ascontiguousarray(t)).to(dev) for t in flat.tubes(cur_xyz, cur_r))
         seg = segment_points(pts, a, b, r1, r2, pt_off, tube_off, max_distance, form, tally=False, outputs=("tube",))
         res = fit_tubes(pts, seg["tube"], a, b, r1, r2, max_relative, min_points, min_spread)
         fit = res["fit"].cpu().numpy()  # the one read-back of an iteration
-        cur_xyz, cur_r = update_vertices(flat, cur_xyz, cur_r, xyz0, radii0, fit, max_ratio, move_axis)
-    report = SkeletonFit(fit, _branch_table(flat, fit, radii0.astype(np.float64), cur_r), flat.tube_off, int(iterations))
+        cur_xyz, cur_r = update_vertices(links, cur_xyz, cur_r, xyz0, radii0, fit, max_ratio, move_axis)
+    report = SkeletonFit(fit, _branch_table(flat, fit, flat.radii, cur_r), flat.tube_off, int(iterations))
     out = flat.rebuild(cur_xyz, cur_r)
     return (out if many else out[0]), report
 
@@ -283,24 +211,16 @@ def summary(fit: SkeletonFit) -> str:
 # ---------------------------------------------------------------------------------------------------------------- cli ---
 DEFAULTS = {"cloud": None, "skeleton": None, "out": None, "iterations": 2, "max_distance": None, "max_relative": 0.5, "centre": False,
             "classes": [0], "device": "cuda:0"}
+USAGE = ("usage: python -m smart_tree_amd.refine cloud=<.npz|.ply> skeleton=<skeleton.npz> out=<dir|.npz> [iterations=2] "
+         "[max_distance=] [max_relative=0.5] [centre=false] [classes=[0]] [device=]")
 
 
 def main(argv=None):
-    from .config import apply_overrides
+    from .config import cloud_command
     from .evaluate import load_any_skeleton
-    from .util.file import load_cloud, save_skeleton_npz
+    from .util.file import save_skeleton_npz
 
-    cfg = apply_overrides(dict(DEFAULTS), argv if argv is not None else sys.argv[1:])
-    unknown = sorted(set(cfg) - set(DEFAULTS))
-    if unknown or cfg["cloud"] is None or cfg["skeleton"] is None or cfg["out"] is None:
-        raise SystemExit("usage: python -m smart_tree_amd.refine cloud=<.npz|.ply> skeleton=<skeleton.npz> out=<dir|.npz> [iterations=2] "
-                         "[max_distance=] [max_relative=0.5] [centre=false] [classes=[0]] [device=]"
-                         + (f"  (unknown: {', '.join(unknown)})" if unknown else ""))
-    dev = torch.device(cfg["device"])
-    cloud = load_cloud(cfg["cloud"]).to_device(dev)
-    if str(cfg["centre"]).lower() in ("true", "1", "yes", "on"):
-        from .dataset.augmentations import CentreCloud
-        cloud = CentreCloud()(cloud)
+    cfg, dev, cloud = cloud_command(argv, DEFAULTS, USAGE)
     if cloud.class_l is not None and cfg["classes"] is not None:
         classes = cfg["classes"] if isinstance(cfg["classes"], (list, tuple)) else [cfg["classes"]]
         cloud = cloud.filter_by_class([int(c) for c in classes])

@@ -237,13 +237,12 @@ def medial_vector_items(cloud, colour=(0.0, 0.0, 0.0)):
 def skeleton_items(skeleton, device=None):
     """The tubes of a `TreeSkeleton`, a `DisjointTreeSkeleton` or the flat arrays of `save_skeleton_npz` (in `skeleton_tubes`
     order), coloured by branch."""
-    from .evaluation import branch_key, skeleton_owners, skeleton_tubes
+    from .data_types.flat import FlatSkeletons
+    from .evaluation import branch_key
 
-    a, b, r1, r2 = skeleton_tubes(skeleton)
-    owner = skeleton_owners(skeleton)
-    ids = np.repeat(branch_key(owner[:, 0], owner[:, 1]), owner[:, 3]).astype(np.int32)
-    if ids.shape[0] != a.shape[0]:
-        raise RuntimeError(f"skeleton_items: {a.shape[0]} tubes for {ids.shape[0]} branch labels")
+    flat = FlatSkeletons([skeleton], "skeleton_items")
+    a, b, r1, r2 = (torch.from_numpy(t) for t in flat.tubes(*flat.float32()))
+    ids = np.repeat(branch_key(flat.rows[:, 1], flat.rows[:, 2]), flat.tubes_of_row).astype(np.int32)
     dev = torch.device(device) if device is not None else torch.device("cuda:0")
     f = lambda t: t.to(dev).float().contiguous()
     return [SegmentItem(f(a), f(b), f(r1).reshape(-1), f(r2).reshape(-1), id_colour(torch.from_numpy(ids).to(dev)))]

@@ -7,13 +7,12 @@ cloud into the frame of the skeleton the pipeline saved for it.  Overrides are p
 
 The reference has `skeleton_to_points` (util/queries.py:139-166): distance, radius and vector to the nearest tube, by a dense
 sweep, and no ids.  `segment_cloud` answers per point which tube wins -- the minimum of |distance to the axis - radius|, ties to
-the lowest tube, exactly as include/smarttree_hip.h states it -- and turns the tube into (tree, branch) through the same owner
-walk the renderer colours tubes with (`evaluation.skeleton_owners`).  A batch of clouds goes through one call, each cloud against
+the lowest tube, exactly as include/smarttree_hip.h states it -- and turns the tube into (tree, branch) through the table of
+branches the renderer colours tubes with (`data_types.flat.FlatSkeletons`).  A batch of clouds goes through one call, each cloud against
 its own trees.  Per-branch statistics come from integer per-tube tallies: identical from run to run.
 """
 from __future__ import annotations
 
-import sys
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Optional
@@ -23,7 +22,8 @@ import torch
 
 from . import _lib
 from .data_types.cloud import Cloud
-from .evaluation import branch_key, skeleton_owners, skeleton_tubes
+from .data_types.flat import FlatSkeletons, points_and_skeletons
+from .evaluation import branch_key
 
 FORMS = {"auto": 0, "dense": 1, "grid": 2}
 UNASSIGNED_KEY = 0x7FFFFFFF  # `to_cloud`'s branch id of a point without a tube (no (tree, branch) below 2^15 trees maps to it)
@@ -141,33 +141,17 @@ class CloudSegmentation:
                                      t("seg_off") if "seg_off" in z.files else None, z["tube_off"] if "tube_off" in z.files else None)
 
 
-def _is_skeleton_list(skeleton) -> bool:
-    return isinstance(skeleton, (list, tuple))
-
-
 def segment_cloud(cloud_or_xyz, skeleton, max_distance=None, form="auto", tally=True, device=None) -> CloudSegmentation:
     """Every point of a `Cloud` (or an [n,3] tensor / array) to the tube, tree and branch of `skeleton`: a `TreeSkeleton`, a
     `DisjointTreeSkeleton`, the flat arrays of `save_skeleton_npz`, or a list of these, one per cloud of a collated `Cloud` (what
     `Pipeline.process_clouds` returns).  `max_distance` (metres from the tube's surface): points further than that stay
     unassigned.  `tally=False` skips the per-branch statistics (their columns are NaN)."""
-    if isinstance(cloud_or_xyz, Cloud):
-        xyz, seg_off = cloud_or_xyz.xyz, cloud_or_xyz.seg_off
-    else:
-        xyz, seg_off = torch.as_tensor(np.asarray(cloud_or_xyz) if not torch.is_tensor(cloud_or_xyz) else cloud_or_xyz), None
-    dev = torch.device(device) if device is not None else xyz.device
-    xyz = xyz.to(dev)
-    skeletons = list(skeleton) if _is_skeleton_list(skeleton) else [skeleton]
-    n_clouds = 1 if seg_off is None else int(seg_off.shape[0]) - 1
-    if len(skeletons) != n_clouds:
-        raise ValueError(f"segment_cloud: {len(skeletons)} skeleton(s) for {n_clouds} cloud(s); a collated Cloud takes a list, one per cloud")
-    tubes = [skeleton_tubes(s) for s in skeletons]
-    owners = [skeleton_owners(s) for s in skeletons]
-    for t, o in zip(tubes, owners):
-        if int(o[:, 3].sum()) != t[0].shape[0]:
-            raise RuntimeError(f"segment_cloud: {t[0].shape[0]} tubes for {int(o[:, 3].sum())} owned by branches")
-    a, b, r1, r2 = (torch.cat([t[k] for t in tubes]) for k in range(4))
-    tube_off = np.cumsum([0] + [t[0].shape[0] for t in tubes]).astype(np.int64)
-    owner = np.concatenate([np.concatenate([np.full((len(o), 1), k, np.int64), o], axis=1) for k, o in enumerate(owners)])  # cloud, tree, id, parent, tubes
+    xyz, seg_off, skeletons, _, _ = points_and_skeletons(cloud_or_xyz, skeleton, device, "segment_cloud")
+    dev = xyz.device
+    flat = FlatSkeletons(skeletons, "segment_cloud")
+    a, b, r1, r2 = (torch.from_numpy(t) for t in flat.tubes(*flat.float32()))
+    tube_off = flat.tube_off
+    owner = np.column_stack([flat.rows[:, :4], flat.tubes_of_row])  # cloud, tree, id, parent, tubes
     batched = seg_off is not None
     res = segment_points(xyz, a, b, r1, r2, seg_off if batched else None,
                          torch.from_numpy(tube_off.astype(np.int32)) if batched else None, max_distance, form, tally)
@@ -242,26 +226,17 @@ def summary(seg: CloudSegmentation) -> str:
 # ---------------------------------------------------------------------------------------------------------------- cli ---
 DEFAULTS = {"cloud": None, "skeleton": None, "out": None, "max_distance": None, "centre": False, "png": None, "width": 1920,
             "height": 1080, "form": "auto", "device": "cuda:0"}
+USAGE = ("usage: python -m smart_tree_amd.segmentation cloud=<.npz|.ply> skeleton=<skeleton.npz> out=<dir|.npz> "
+         "[max_distance=0.1] [centre=false] [png=<file>] [width=1920] [height=1080] [form=auto|dense|grid] [device=]")
 
 
 def main(argv=None) -> CloudSegmentation:
-    from .config import apply_overrides
+    from .config import cloud_command
     from .evaluate import load_any_skeleton
-    from .util.file import load_cloud
 
-    cfg = apply_overrides(dict(DEFAULTS), argv if argv is not None else sys.argv[1:])
-    unknown = sorted(set(cfg) - set(DEFAULTS))
-    if unknown or cfg["cloud"] is None or cfg["skeleton"] is None or cfg["out"] is None:
-        raise SystemExit("usage: python -m smart_tree_amd.segmentation cloud=<.npz|.ply> skeleton=<skeleton.npz> out=<dir|.npz> "
-                         "[max_distance=0.1] [centre=false] [png=<file>] [width=1920] [height=1080] [form=auto|dense|grid] [device=]"
-                         + (f"  (unknown: {', '.join(unknown)})" if unknown else ""))
+    cfg, dev, cloud = cloud_command(argv, DEFAULTS, USAGE)
     if str(cfg["form"]) not in FORMS:
         raise SystemExit(f"segmentation: form must be one of {', '.join(FORMS)}")
-    dev = torch.device(cfg["device"])
-    cloud = load_cloud(cfg["cloud"]).to_device(dev)
-    if str(cfg["centre"]).lower() in ("true", "1", "yes", "on"):
-        from .dataset.augmentations import CentreCloud
-        cloud = CentreCloud()(cloud)
     skeleton = load_any_skeleton(cfg["skeleton"])
     seg = segment_cloud(cloud, skeleton, max_distance=None if cfg["max_distance"] is None else float(cfg["max_distance"]),
                         form=str(cfg["form"]), device=dev)

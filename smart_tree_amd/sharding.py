@@ -12,10 +12,12 @@ from __future__ import annotations
 
 from typing import List, Sequence
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 from .data_types.branch import BranchSkeleton
+from .data_types.flat import FlatSkeletons
 from .data_types.tree import DisjointTreeSkeleton, TreeSkeleton
 
 
@@ -29,14 +31,10 @@ def pack_skeleton(sk: DisjointTreeSkeleton, cloud_id: int = 0):
     fast = sk.pack(cloud_id) if hasattr(sk, "pack") else None  # DeviceSkeleton: straight from its packed host arrays
     if fast is not None:
         return fast
-    rows, geom, off = [], [], 0
-    for tree in sk.skeletons:
-        for b in tree.branches.values():
-            rows.append((cloud_id, tree._id, b._id, b.parent_id, off, len(b)))
-            geom.append(torch.cat((b.xyz.float(), b.radii.reshape(-1, 1).float()), dim=1))
-            off += len(b)
-    table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 6)
-    return table, (torch.cat(geom) if geom else torch.zeros((0, 4), dtype=torch.float32))
+    flat = FlatSkeletons([sk], "pack_skeleton")
+    xyz, radii = flat.float32()
+    table = np.column_stack([np.full(len(flat.rows), cloud_id, np.int64), flat.label, flat.rows[:, 2:]])
+    return torch.from_numpy(table), torch.from_numpy(np.column_stack([xyz, radii]))
 
 
 def unpack_skeletons(table: torch.Tensor, geom: torch.Tensor) -> dict:

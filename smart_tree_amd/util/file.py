@@ -160,14 +160,9 @@ def load_skeleton(path):
 
 def save_skeleton_npz(path, skeleton) -> None:
     """Flat arrays: per branch (tree id, branch id, parent id, offset, length) + concatenated xyz / radii."""
-    rows, xyz, radii, off = [], [], [], 0
-    for tree in skeleton.skeletons:
-        for b in tree.branches.values():
-            rows.append((tree._id, b._id, b.parent_id, off, len(b)))
-            xyz.append(b.xyz.numpy())
-            radii.append(b.radii.reshape(-1).numpy())
-            off += len(b)
+    from ..data_types.flat import FlatSkeletons
+
+    flat = FlatSkeletons([skeleton], "save_skeleton_npz")
+    xyz, radii = flat.float32()
     Path(path).parent.mkdir(parents=True, exist_ok=True)
-    np.savez(path, branches=np.asarray(rows, dtype=np.int64).reshape(-1, 5),
-             xyz=np.concatenate(xyz) if xyz else np.zeros((0, 3), np.float32),
-             radii=np.concatenate(radii) if radii else np.zeros((0,), np.float32))
+    np.savez(path, branches=np.column_stack([flat.label, flat.rows[:, 2:]]), xyz=xyz, radii=radii)

@@ -16,6 +16,7 @@ from smart_tree_amd import refine as R
 from smart_tree_amd.data_types.branch import BranchSkeleton
 from smart_tree_amd.data_types.cloud import Cloud
 from smart_tree_amd.data_types.tree import DisjointTreeSkeleton, TreeSkeleton
+from smart_tree_amd.data_types.flat import FlatSkeletons
 from smart_tree_amd.evaluation import skeleton_tubes
 
 import fit_oracle as fo
@@ -278,6 +279,16 @@ def _two_branches():
     return DisjointTreeSkeleton([TreeSkeleton(0, {0: trunk, 1: child})])
 
 
+class _FitTable(FlatSkeletons):
+    """The table as `refine_skeleton` works on it: float32 vertices and the links of every vertex to its tubes."""
+
+    def __init__(self, skeletons):
+        super().__init__(skeletons)
+        self.xyz, self.radii = self.float32()
+        self.links = R.vertex_links(self)
+        self.lo, self.hi, self.pinned = self.links
+
+
 def _rows(*rows):
     """fit rows (N, R, offset, status) -> [m,8]."""
     out = np.zeros((len(rows), 8))
@@ -288,7 +299,7 @@ def _rows(*rows):
 
 def test_update_rules():
     sk = _two_branches()
-    flat = R._Flat([sk])
+    flat = _FitTable([sk])
     assert flat.lo.tolist() == [-1, 0, 1, 2, -1, 3, 4] and flat.hi.tolist() == [0, 1, 2, -1, 3, 4, -1]
     assert flat.pinned.tolist() == [False, False, False, False, True, False, False] and flat.tube_off.tolist() == [0, 5]
     fit = _rows((30, 0.22, (0.01, 0, 0), 2),      # tube 0
@@ -296,7 +307,7 @@ def test_update_rules():
                 (50, 0.90, (0, 0, 0), 1),         # tube 2: radius only, far above the prior
                 (20, 0.06, (0, 0, 0.5), 2),       # tube 3: an offset ten times the radius
                 (5, 0.01, (0, 0.3, 0), 0))        # tube 4: not fitted
-    xyz, radii = R.update_vertices(flat, flat.xyz, flat.radii, flat.xyz, flat.radii, fit)
+    xyz, radii = R.update_vertices(flat.links, flat.xyz, flat.radii, flat.xyz, flat.radii, fit)
     assert xyz.dtype == F and radii.dtype == F
     # vertex 0: tube 0 alone.  vertex 1: the weighted mean of tubes 0 and 1
     assert radii[0] == F(0.22) and np.allclose(xyz[0], [0.01, 0, 0])
@@ -312,14 +323,14 @@ def test_update_rules():
     # vertex 6: no fitted tube
     assert radii[6] == F(0.05) and xyz[6].tolist() == [2, 2, 0]
     # downwards: the clamp at prior / max_ratio; another ratio; move_axis off
-    low = R.update_vertices(flat, flat.xyz, flat.radii, flat.xyz, flat.radii, _rows((9, 0.01, (0, 0, 0), 1), *[(0, 0, (0, 0, 0), 0)] * 4))
+    low = R.update_vertices(flat.links, flat.xyz, flat.radii, flat.xyz, flat.radii, _rows((9, 0.01, (0, 0, 0), 1), *[(0, 0, (0, 0, 0), 0)] * 4))
     assert low[1][0] == F(0.1) and low[1][1] == F(0.1) and low[1][2] == F(0.2)
-    wide = R.update_vertices(flat, flat.xyz, flat.radii, flat.xyz, flat.radii, fit, max_ratio=10.0)
+    wide = R.update_vertices(flat.links, flat.xyz, flat.radii, flat.xyz, flat.radii, fit, max_ratio=10.0)
     assert wide[1][3] == F(0.9) and wide[1][2] == F(0.78)
-    still = R.update_vertices(flat, flat.xyz, flat.radii, flat.xyz, flat.radii, fit, move_axis=False)
+    still = R.update_vertices(flat.links, flat.xyz, flat.radii, flat.xyz, flat.radii, fit, move_axis=False)
     assert np.array_equal(still[0], flat.xyz) and np.array_equal(still[1], radii)
     # the limits hold against the PRIOR over several rounds: a second update from the moved state cannot leave the prior's reach
-    again = R.update_vertices(flat, xyz, radii, flat.xyz, flat.radii, fit)
+    again = R.update_vertices(flat.links, xyz, radii, flat.xyz, flat.radii, fit)
     assert np.linalg.norm(again[0] - flat.xyz, axis=1).max() <= flat.radii.max() + 1e-6 and np.allclose(again[0][5], [1, 2, 0.05])
     assert again[1][2] == F(0.4)
 
@@ -461,20 +472,20 @@ def test_fit_report_round_trips(backend, tmp_path):
 # ------------------------------------------------------------------------------- 7: against ground truth ---
 def _oracle_refine(xyz, skeleton, iterations=2):
     """refine_skeleton with the two oracles in the kernels' places (the vertex update is host code either way)."""
-    flat = R._Flat([skeleton])
+    flat = _FitTable([skeleton])
     cur_xyz, cur_r, fit = flat.xyz.copy(), flat.radii.copy(), None
     for _ in range(iterations):
         a, b, r1, r2 = flat.tubes(cur_xyz, cur_r)
         tube = oracle_segment(xyz, a, b, r1, r2, check64=False)["tube"]
         fit = fo.fit(xyz, tube, a, b, r1, r2)[1]
-        cur_xyz, cur_r = R.update_vertices(flat, cur_xyz, cur_r, flat.xyz, flat.radii, fit)
+        cur_xyz, cur_r = R.update_vertices(flat.links, cur_xyz, cur_r, flat.xyz, flat.radii, fit)
     return cur_xyz, cur_r, fit
 
 
 def _errors(truth, xyz, radii, fit):
     """Over the vertices of true radius >= 0.02 m that touch a fully fitted tube: (median relative radius error, median distance
     from the true axis in true radii, the share of the >= 0.02 m vertices these are)."""
-    flat = R._Flat([truth])
+    flat = _FitTable([truth])
     status = np.concatenate([fit[:, 7], [0.0]])
     touched = (status[flat.lo] == 2) | (status[flat.hi] == 2)
     big = flat.radii >= 0.02
@@ -494,10 +505,10 @@ def test_refinement_approaches_the_ground_truth(backend, seed):
     """Measured, the kernels and the oracle pipeline alike: seed 3 (147 tubes) radius error 0.1299 -> 0.0099, axis distance 0.2000 ->
     0.0116 radii, 92 % of the vertices; seed 11 (209 tubes) 0.1371 -> 0.0102, 0.2000 -> 0.0112, 90 %."""
     xyz, truth, guess = _truth_case(seed, str(backend))
-    start = R._Flat([guess])
+    start = _FitTable([guess])
     o_xyz, o_r, o_fit = _oracle_refine(xyz, guess)
     refined, fit = R.refine_skeleton(_t(xyz, backend), guess, iterations=2)
-    got = R._Flat([refined])
+    got = _FitTable([refined])
     before = _errors(truth, start.xyz, start.radii, fit.tubes)
     after = _errors(truth, got.xyz, got.radii, fit.tubes)
     o_before = _errors(truth, start.xyz, start.radii, o_fit)
@@ -586,8 +597,8 @@ def _pipeline_case(dev, tmp_path, capsys):
     saved = R.SkeletonFit.load(tmp_path / "out" / "skeleton_fit.npz")
     np.testing.assert_array_equal(saved.tubes.view(np.uint64), want_fit.tubes.view(np.uint64))
     from smart_tree_amd.evaluate import load_any_skeleton
-    flat = R._Flat([load_any_skeleton(tmp_path / "out" / "skeleton.npz")])  # what was saved is the refined skeleton
-    got = R._Flat([refined])
+    flat = _FitTable([load_any_skeleton(tmp_path / "out" / "skeleton.npz")])  # what was saved is the refined skeleton
+    got = _FitTable([refined])
     assert np.array_equal(flat.xyz, got.xyz) and np.array_equal(flat.radii, got.radii)
     # other settings reach the call
     pipe.refine_iterations, pipe.refine_max_relative, pipe.save_outputs = 1, 0.2, False
@@ -612,14 +623,14 @@ def _pipeline_case(dev, tmp_path, capsys):
     assert _sig(cli) == _sig(refined)
     np.testing.assert_array_equal(cli_fit.tubes.view(np.uint64), want_fit.tubes.view(np.uint64))
     assert sorted(p.name for p in (tmp_path / "cli").iterdir()) == ["skeleton.npz", "skeleton_fit.npz"]
-    back = R._Flat([load_any_skeleton(tmp_path / "cli" / "skeleton.npz")])
+    back = _FitTable([load_any_skeleton(tmp_path / "cli" / "skeleton.npz")])
     assert np.array_equal(back.xyz, got.xyz) and np.array_equal(back.radii, got.radii)
     text = capsys.readouterr().out
     assert "full fit" in text and "points used:" in text and "mean relative radius change:" in text
     R.main([f"cloud={tmp_path / 'wood.npz'}", f"skeleton={tmp_path / 'raw.npz'}", f"out={tmp_path / 'one.npz'}", "iterations=1", "max_relative=0.2",
             "classes=[0]", f"device={dev}"])
-    one = R._Flat([load_any_skeleton(tmp_path / "one.npz")])
-    assert np.array_equal(one.xyz, R._Flat([other]).xyz)
+    one = _FitTable([load_any_skeleton(tmp_path / "one.npz")])
+    assert np.array_equal(one.xyz, _FitTable([other]).xyz)
     with pytest.raises(SystemExit):
         R.main(["cloud=x.npz"])
 

@@ -15,6 +15,7 @@ from smart_tree_amd import _lib
 from smart_tree_amd import inventory as I
 from smart_tree_amd.data_types.branch import BranchSkeleton
 from smart_tree_amd.data_types.cloud import Cloud
+from smart_tree_amd.data_types.flat import FlatSkeletons
 from smart_tree_amd.data_types.tree import DisjointTreeSkeleton, TreeSkeleton
 
 import inventory_oracle as io
@@ -269,7 +270,7 @@ def _no_points(T, layers=8):
 
 def test_branch_metrics_by_hand():
     tree = _hand_tree()
-    flat = I._Flat([tree])
+    flat = FlatSkeletons([tree])
     rows, orphans = I.branch_table(flat, points=np.array([40.0, 30.0, 20.0, 10.0]))
     col = lambda name: rows[:, I.BRANCH_COLUMNS.index(name)]
     assert rows.shape == (4, 14) and col("branch").tolist() == [0, 1, 2, 5] and col("parent").tolist() == [-1, 0, 1, 99]
@@ -296,7 +297,7 @@ def test_branch_metrics_by_hand():
 def test_tree_metrics_by_hand():
     tall, short = _hand_tree(0), _hand_tree(1, top=1.25, shift=(5.0, -2.0, 0.0))
     sk = DisjointTreeSkeleton([tall, short])
-    flat = I._Flat([sk])
+    flat = FlatSkeletons([sk])
     assert flat.tree_rows.tolist() == [[0, 0], [0, 1]]
     rows, _ = I.branch_table(flat)
     box, counts, area, profile = _no_points(2)

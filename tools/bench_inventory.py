@@ -24,6 +24,7 @@ import bench
 from smart_tree_amd import inventory as I
 from smart_tree_amd import segmentation as S
 from smart_tree_amd.data_types.cloud import Cloud
+from smart_tree_amd.data_types.flat import FlatSkeletons
 from smart_tree_amd.data_types.tree import DisjointTreeSkeleton
 from smart_tree_amd.dataset.augmentations import CentreCloud
 from smart_tree_amd.synthetic import sample_tree_cloud
@@ -86,7 +87,7 @@ def measure(cloud, skeletons, args, warmup, repeats):
     pts = cloud.xyz
     seg_fn = lambda: S.segment_cloud(cloud, skeletons, tally=False)
     seg = S.segment_cloud(cloud, skeletons)
-    flat = I._Flat(skeletons if isinstance(skeletons, list) else [skeletons])
+    flat = FlatSkeletons(skeletons if isinstance(skeletons, list) else [skeletons])
     T = len(flat.tree_rows)
     rows_fn = lambda: I.point_rows(flat, seg.tree_id, cloud.seg_off, pts.device)
     row = rows_fn()

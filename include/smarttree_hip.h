@@ -43,7 +43,8 @@ extern "C" {
  * 116: the neighbour searches serve a run of queries per wavefront (no signature, workspace size or result changed).
  * 117: st_scan_u32_dev and st_fill_u32_len added for the primitive-level tests; st_sort_pairs_u32 ignores the key bits at and
  * above key_bits (before: it ordered by whole bytes); the coordinate hash probes every slot of a table of up to 4096 slots (no
- * existing signature changed). */
+ * existing signature changed).
+ * 118: st_scan_cast_seg and its size query st_scan_cast_workspace_bytes added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -729,6 +730,44 @@ int st_ground_model(const float* pts, int64_t n, const int32_t* seg_off, int nse
 int st_ground_height(const float* pts, int64_t m, const int32_t* seg_off, int nseg, int up, float cell, float tol, const float* origin,
                      const int32_t* dims_host, const int64_t* cell_off_host, const float* surface, float* height, uint8_t* is_ground,
                      float* ground, void* stream);
+
+/* ---- virtual laser scanner: beams against the tubes of a skeleton, first hits as labelled points (csrc/scan.hip) -----------
+ * replaces: nothing -- the reference has no scanner model; its training clouds are an external download.
+ *
+ * Tubes a, b [m,3], r1, r2 [m] (device), tube_seg_off [nseg + 1] int32 (device; NULL with nseg = 1), 1 <= nseg <= st_abi_entries(2);
+ * tube_class [m] uint8 (0 wood, anything else leaf; NULL: all wood) and tube_branch [m] int32 (NULL: every branch id is -1).
+ * scanners [n_scanners] and ray_off [n_scanners + 1] are HOST arrays, read before the call returns; a scanner's cloud may not
+ * decrease along the table, and ray_off must be the running sum of n_az * n_el from 0.  Ray k of a scanner is beam
+ * (i, j) = (k / n_el, k % n_el): az = az0 + i daz, el = el0 + j del (radians), direction (cos el cos az, cos el sin az, sin el).
+ * Surface, solve, winner and the two forms: the head of csrc/scan.hip.  In short: the surface of a tube is the zero set of the
+ * point-to-tube residual (frustum side and the two end spheres outside it; a zero-length tube is a sphere); a hit is the smallest
+ * root s with min_range <= s <= max_range over the tubes of the scanner's cloud, ties to the lowest tube; a ray from inside a tube
+ * returns its far wall; a tube with a non-finite value or a negative radius is never hit.  form: 0 auto, 1 dense, 2 grid -- the
+ * same bits in every output.
+ * Per ray (R = ray_off[n_scanners] rows; each may be NULL): dir [R,3], range [R] (+inf without a hit), tube [R] int32 (-1 without).
+ * Per hit, compacted in ray order (room for R rows; each may be NULL): xyz [.,3] = the hit moved along the ray by range_noise x a
+ * normal draw (Philox4x32-10, key = seed, counter = (k, 0, 0, 0)); medial_vector [.,3] = the axis point minus the un-noised hit
+ * (0 for a leaf); class_l float32 (0 / 1); branch_ids int32 (-1 for a leaf); segment int32 (the tube); ray int32; n_hits int64 [1]
+ * (device).
+ * Enqueue-only: no allocation, no read-back, no wait.  Refused, nothing launched (-1): m outside [0, 2^31), nseg out of range or
+ * nseg > 1 without tube_seg_off, n_scanners outside [0, ST_SCAN_MAX_SCANNERS], a scanner with a non-finite position, angle or
+ * range_noise, with NaN or negative ranges or max_range < min_range, with a negative beam count or a cloud out of range or below
+ * its predecessor's, 2^31 - 1 beams or more, a ray_off that is not the running sum, a form outside 0..2; a workspace below
+ * st_scan_cast_workspace_bytes(R, m, n_scanners, nseg) (-2; the size query returns -1 for sizes the call refuses). */
+#define ST_SCAN_MAX_SCANNERS 4096 /* the table travels as kernel arguments, 32 scanners per launch: 129 small launches at the limit */
+typedef struct StScanner {
+    int32_t cloud, n_az, n_el, reserved;
+    float position[3];
+    float az0, daz, el0, del;
+    float min_range, max_range, range_noise;
+    uint64_t seed;
+} StScanner;
+int64_t st_scan_cast_workspace_bytes(int64_t n_rays, int64_t m, int n_scanners, int nseg);
+int st_scan_cast_seg(const float* a, const float* b, const float* r1, const float* r2, int64_t m, const int32_t* tube_seg_off, int nseg,
+                     const uint8_t* tube_class, const int32_t* tube_branch, const StScanner* scanners, int n_scanners,
+                     const int64_t* ray_off, int form, float* dir, float* range, int32_t* tube, float* xyz, float* medial_vector,
+                     float* class_l, int32_t* branch_ids, int32_t* segment, int32_t* ray, int64_t* n_hits, void* ws, int64_t ws_bytes,
+                     void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,7 @@
 // LDS (<= SY_LDS_CDF entries, 16 KB; a larger table is searched in global memory) -- the rows would not fit; points of any
 // other tree the workgroup straddles search that tree's cdf in global memory.  Bound by the HBM writes and ~7 transcendentals.
 #include "st_common.h"
+#include "st_philox.h"
 
 #define SY_BLOCK 256
 #define SY_PPT 8            // points per thread: one cdf staging per 2048 points
@@ -45,36 +46,6 @@ struct SyTrees {  // host values, passed by value: the launch needs no upload an
     float noise[SY_MAX_TREES], sigma[SY_MAX_TREES];
     int32_t n_trees;
 };
-
-struct SyWords { uint32_t w0, w1, w2, w3; };
-
-__host__ __device__ __forceinline__ SyWords sy_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; round++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return SyWords{c0, c1, c2, c3};
-}
-
-#define SY_2POW_M24 5.9604644775390625e-8f
-#define SY_TWO_PI 6.28318530717958647692f
-
-__device__ __forceinline__ float sy_uniform(uint32_t w) { return (float)(w >> 8) * SY_2POW_M24; }
-__device__ __forceinline__ void sy_normal_pair(uint32_t wa, uint32_t wb, float& n0, float& n1) {
-    const float u1 = (float)((wa >> 8) + 1u) * SY_2POW_M24;  // (0, 1]: the logarithm never sees 0
-    const float u2 = (float)((wb >> 8) + 1u) * SY_2POW_M24;
-    const float m = sqrtf(-2.0f * logf(u1));
-    const float phi = SY_TWO_PI * u2;
-    n0 = m * cosf(phi);
-    n1 = m * sinf(phi);
-}
 
 // First j in [0, n) with cdf[j] > w; n - 1 when there is none (w == 0xFFFFFFFF).  n >= 1.
 __device__ __forceinline__ int sy_pick(const uint32_t* cdf, int n, uint32_t w) {

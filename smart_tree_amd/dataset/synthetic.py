@@ -8,6 +8,8 @@ medial vector, branch id), no files, no upload of points.
 * `tree_skeleton(segs, tree_id)`: the branches of a `grow_tree` result.
 * `segment_table(segs)`: what the kernel reads of one tree.
 * `generate_trees(seeds, n_points, ...)`: one batched `Cloud` plus the skeletons.
+* `scan_trees(seeds, scanners, ...)`: the same trees seen by a ring of virtual laser scanners (smart_tree_amd/scan.py): one side
+  of a stem per position, density falling with the range, shadows.
 * `SyntheticTreeDataset`: `TreeDataset`'s item layout from trees generated on the fly, fresh ones every training epoch.
 * `python -m smart_tree_amd.dataset.generate` writes a folder of them (dataset/generate.py).
 
@@ -218,6 +220,42 @@ def generate_trees(seeds, n_points, *, scale=1.0, noise=0.002, foliage_fraction=
     return cloud, skeletons
 
 
+def leaf_centres(segs: TreeSegments, seed: int, leaves_per_tip: int, sigma: float) -> np.ndarray:
+    """[T * leaves_per_tip, 3] float32: per tip (end point of a segment without children, in list order) `leaves_per_tip` centres,
+    tip + sigma * N(0, 1) per axis, from numpy's `default_rng(seed mod 2^64)`."""
+    tips = np.asarray(segs.b[segs.is_tip], dtype=np.float64).reshape(-1, 3)
+    rng = np.random.default_rng(int(seed) & _M64)
+    return (np.repeat(tips, int(leaves_per_tip), axis=0) + float(sigma) * rng.standard_normal((len(tips) * int(leaves_per_tip), 3))).astype(np.float32)
+
+
+def scan_trees(seeds, scanners=3, *, step_deg=0.1, radius=6.0, height=1.5, scale=1.0, max_depth=7, leaves_per_tip=0, leaf_radius=0.02,
+               foliage_sigma=None, range_noise=0.002, form="auto", device=None):
+    """Trees `seeds`, grown exactly as `generate_trees` grows them, each scanned by `scanners` positions on a ring of `radius`
+    metres about its box, `height` above its lowest point, in beams `step_deg` apart (`scan.scanner_ring`; scanner k of tree `seed`
+    draws its range noise with `seed + k`).  `leaves_per_tip` > 0 hangs that many spheres of `leaf_radius` about every tip, their
+    centres drawn on the host (`leaf_centres`; foliage_sigma=None: 0.08 * scale); they are class 1, shadow the wood and carry no
+    medial vector.  `max_depth` may be one value or one per tree.  Returns what `generate_trees` returns: one batched `Cloud` and
+    the ground-truth skeletons."""
+    from ..scan import scan_skeletons, scanner_ring, skeleton_box
+
+    seeds = [int(s) for s in np.atleast_1d(np.asarray(seeds, dtype=object))]
+    B = len(seeds)
+    if B > MAX_TREES:
+        raise ValueError(f"scan_trees: at most {MAX_TREES} trees per call (got {B})")
+    dev = torch.device(device) if device is not None else torch.device("cuda:0")
+    sigma = 0.08 * scale if foliage_sigma is None else foliage_sigma
+    grown = [grow_tree(s & 0xFFFFFFFF, scale, int(d)) for s, d in zip(seeds, _per_tree(max_depth, B, "max_depth"))]
+    skeletons = [tree_skeleton(g, tree_id=i) for i, g in enumerate(grown)]
+    leaves = None
+    if int(leaves_per_tip) > 0:
+        centres = [leaf_centres(g, s, leaves_per_tip, sigma) for g, s in zip(grown, seeds)]
+        leaves = [(c, np.full(len(c), leaf_radius, np.float32)) for c in centres]
+    rings = [scanner_ring(int(scanners), radius, height, skeleton_box(sk, None if leaves is None else leaves[i]), step_deg, seed=seeds[i],
+                          range_noise=range_noise) for i, sk in enumerate(skeletons)]
+    cloud, _ = scan_skeletons(skeletons, rings, leaves, form, dev)
+    return cloud, skeletons
+
+
 # --------------------------------------------------------------------------------------------------------- dataset ---
 def _mix64(x: int) -> int:
     """splitmix64's finaliser."""
@@ -240,11 +278,14 @@ class SyntheticTreeDataset(TreeDataset):
     """`TreeDataset`'s items -- `((inputs, targets), coords, loss_mask, name)` -- from trees generated on the device instead of
     files: item `idx` is the tree `item_seed(seed, mode, idx, epoch)`, through the same augmentation, whole-cloud voxelisation
     and gather.  `epoch` is 0 for validation and test (their trees are fixed) and what `set_epoch` last set in train (fresh
-    trees every epoch; a resumed run asks for the same epoch's trees again).  `name` is `synthetic_<mode>_<seed>`."""
+    trees every epoch; a resumed run asks for the same epoch's trees again).  `name` is `synthetic_<mode>_<seed>`.
+    `scan`: None, or a dict of `scan_trees` keywords (`scanners`, `step_deg`, `radius`, ...): the item is then the tree as a ring of
+    virtual scanners sees it (`scale` and `max_depth` are the dataset's own; `n_points`, `noise` and `foliage_fraction` do not
+    apply)."""
 
     def __init__(self, voxel_size, mode: str, length: int, input_features, target_features, augmentation=None, seed: int = 0,
                  n_points: int = 100_000, scale: float = 1.0, noise: float = 0.002, foliage_fraction: float = 0.3,
-                 max_depth: int = 7, device=None):
+                 max_depth: int = 7, device=None, scan=None):
         if mode not in MODES:
             raise ValueError(f"SyntheticTreeDataset: mode must be train / validation / test, got {mode!r}")
         self.voxel_size = voxel_size
@@ -257,6 +298,9 @@ class SyntheticTreeDataset(TreeDataset):
         self.seed, self.epoch = int(seed), 0
         self.tree_args = dict(n_points=int(n_points), scale=scale, noise=noise, foliage_fraction=foliage_fraction, max_depth=max_depth)
         self.cache = None
+        self.scan = None if scan is None else dict(scan)
+        if self.scan is not None and {"scale", "max_depth", "device"} & set(self.scan):
+            raise ValueError("SyntheticTreeDataset: scale, max_depth and device are the dataset's own arguments, not keys of scan")
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch) if self.mode == "train" else 0
@@ -267,7 +311,11 @@ class SyntheticTreeDataset(TreeDataset):
     def cloud(self, idx: int) -> Cloud:
         if not 0 <= idx < self.length:
             raise IndexError(idx)
-        cld, _ = generate_trees([self.tree_seed(idx)], device=self.device, **self.tree_args)
+        if self.scan is not None:
+            cld, _ = scan_trees([self.tree_seed(idx)], scale=self.tree_args["scale"], max_depth=self.tree_args["max_depth"],
+                                device=self.device, **self.scan)
+        else:
+            cld, _ = generate_trees([self.tree_seed(idx)], device=self.device, **self.tree_args)
         cld.seg_off = None  # one tree: a plain cloud, as a file would give
         return cld
 

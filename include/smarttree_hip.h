@@ -44,7 +44,8 @@ extern "C" {
  * 117: st_scan_u32_dev and st_fill_u32_len added for the primitive-level tests; st_sort_pairs_u32 ignores the key bits at and
  * above key_bits (before: it ordered by whole bytes); the coordinate hash probes every slot of a table of up to 4096 slots (no
  * existing signature changed).
- * 118: st_scan_cast_seg and its size query st_scan_cast_workspace_bytes added (no existing signature changed). */
+ * 118: st_scan_cast_seg and its size query st_scan_cast_workspace_bytes added (no existing signature changed).
+ * 119: st_beam_tally_seg and its size query st_beam_tally_workspace_bytes added (no existing signature changed). */
 int st_version(void);
 /* Array lengths this build of the library reads / writes, so that a caller can check them at run time instead of trusting the
  * header it was compiled against: what = 0 -> int64 entries of `stats_host` (st_skeleton_components*, st_sssp, st_tree_distance,
@@ -768,6 +769,37 @@ int st_scan_cast_seg(const float* a, const float* b, const float* r1, const floa
                      const int64_t* ray_off, int form, float* dir, float* range, int32_t* tube, float* xyz, float* medial_vector,
                      float* class_l, int32_t* branch_ids, int32_t* segment, int32_t* ray, int64_t* n_hits, void* ws, int64_t ws_bytes,
                      void* stream);
+
+/* Beam occupancy (csrc/occupancy.hip): every beam of a scan walked through a voxel grid and tallied per cell.
+ *
+ * origins [n_origins,3] float32 (device); per beam (device, n_beams rows) origin_idx int32, dir [.,3] float32 (unit), range float32
+ * (>= 0 a return, +inf no return).  grids [n_grids] and beam_off [n_grids + 1] are HOST arrays, read before the call returns:
+ * beams beam_off[g] .. beam_off[g + 1] - 1 belong to grid g (beam_off[0] = 0, beam_off[n_grids] = n_beams, not decreasing);
+ * 1 <= n_grids <= st_abi_entries(2), 1 <= dim <= 1024 per axis, cell > 0, fewer than 2^31 cells in all.  max_range >= 0 (+inf
+ * allowed) ends every beam's free part; behind != 0 also counts, per cell, the returns that ended before it.
+ * Per cell, the grids' cells concatenated in table order, cell (x, y, z) of a grid at (x dim_y + y) dim_z + z (device, zeroed by the
+ * call): enter uint32 (free beams that entered), hit uint32 (returns that ended there), behind uint32, path uint64 (free path in
+ * units of cell / 65536).  Per beam (may be NULL): hit_cell int32, the cell inside the beam's grid, or -1.  counters uint32 [2]
+ * (device): [0] n_bad -- beams with a non-finite origin, direction or range, a negative range, an origin_idx outside the table or
+ * |dir|^2 outside [0.998, 1.002]; they touch nothing -- and [1] n_outside, good beams that never touch their grid.
+ * The walk, its tie and boundary rules and the chord's rounding: the head of csrc/occupancy.hip.  form: 0 auto, 1 aggregated (the
+ * lanes of a wavefront that stand in one cell share one atomic per field), 2 plain -- the same bits in every output.
+ * Enqueue-only: no allocation, no read-back, no wait.  Refused, nothing launched (-1): n_beams or n_origins outside [0, 2^31),
+ * n_grids out of range, a grid with a dim outside 1..1024, a cell that is not finite and > 0 or a non-finite corner, 2^31 cells or
+ * more, a beam_off that does not run from 0 to n_beams or decreases, a max_range that is NaN or negative, a form outside 0..2, a
+ * NULL required array; a workspace below st_beam_tally_workspace_bytes(n_beams, n_grids) (-2; the size query returns -1 for
+ * sizes the call refuses). */
+typedef struct StVoxelGrid {
+    float lo[3];
+    float cell;
+    int32_t dim[3];
+    int32_t reserved;
+} StVoxelGrid;
+int64_t st_beam_tally_workspace_bytes(int64_t n_beams, int n_grids);
+int st_beam_tally_seg(const float* origins, int64_t n_origins, const int32_t* origin_idx, const float* dir, const float* range,
+                      int64_t n_beams, const StVoxelGrid* grids, int n_grids, const int64_t* beam_off, float max_range, int behind,
+                      int form, uint32_t* enter, uint32_t* hit, uint32_t* behind_out, uint64_t* path, int32_t* hit_cell,
+                      uint32_t* counters, void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -153,6 +153,8 @@ SIGNATURES = {
     "st_ground_height": (c_int, [P, I64, P, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P, P]),
     "st_scan_cast_workspace_bytes": (I64, [I64, I64, c_int, c_int]),
     "st_scan_cast_seg": (c_int, [P, P, P, P, I64, P, c_int, P, P, P, c_int, P, c_int, P, P, P, P, P, P, P, P, P, P, P, I64, P]),
+    "st_beam_tally_workspace_bytes": (I64, [I64, c_int]),
+    "st_beam_tally_seg": (c_int, [P, I64, P, P, P, I64, P, c_int, P, c_float, c_int, c_int, P, P, P, P, P, P, P, I64, P]),
 }
 
 
@@ -181,7 +183,7 @@ ENQUEUE_ONLY = frozenset({
     "st_bridge_components_workspace_bytes", "st_segment_workspace_bytes", "st_segment_points_seg",
     "st_fit_tubes_workspace_bytes", "st_fit_tubes", "st_tree_tally_workspace_bytes", "st_tree_tally",
     "st_ground_workspace_bytes", "st_ground_extent", "st_ground_model", "st_ground_height",
-    "st_scan_cast_workspace_bytes", "st_scan_cast_seg",
+    "st_scan_cast_workspace_bytes", "st_scan_cast_seg", "st_beam_tally_workspace_bytes", "st_beam_tally_seg",
     "st_sparse_conv_mfma_list_fwd", "st_sparse_conv_b3_list_fwd", "st_sparse_conv_f16_list_fwd", "st_pointwise_mlp_heads_keep", "st_move_rows_list",
 })
 
@@ -202,6 +204,11 @@ class StScanner(ctypes.Structure):
     _fields_ = [("cloud", ctypes.c_int32), ("n_az", ctypes.c_int32), ("n_el", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("position", c_float * 3), ("az0", c_float), ("daz", c_float), ("el0", c_float), ("del_", c_float),
                 ("min_range", c_float), ("max_range", c_float), ("range_noise", c_float), ("seed", ctypes.c_uint64)]
+
+
+class StVoxelGrid(ctypes.Structure):
+    """One grid of st_beam_tally_seg (include/smarttree_hip.h)."""
+    _fields_ = [("lo", c_float * 3), ("cell", c_float), ("dim", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32)]
 
 
 class _Bound:

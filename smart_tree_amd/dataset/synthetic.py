@@ -229,13 +229,14 @@ def leaf_centres(segs: TreeSegments, seed: int, leaves_per_tip: int, sigma: floa
 
 
 def scan_trees(seeds, scanners=3, *, step_deg=0.1, radius=6.0, height=1.5, scale=1.0, max_depth=7, leaves_per_tip=0, leaf_radius=0.02,
-               foliage_sigma=None, range_noise=0.002, form="auto", device=None):
+               foliage_sigma=None, range_noise=0.002, form="auto", device=None, beams=False):
     """Trees `seeds`, grown exactly as `generate_trees` grows them, each scanned by `scanners` positions on a ring of `radius`
     metres about its box, `height` above its lowest point, in beams `step_deg` apart (`scan.scanner_ring`; scanner k of tree `seed`
     draws its range noise with `seed + k`).  `leaves_per_tip` > 0 hangs that many spheres of `leaf_radius` about every tip, their
     centres drawn on the host (`leaf_centres`; foliage_sigma=None: 0.08 * scale); they are class 1, shadow the wood and carry no
     medial vector.  `max_depth` may be one value or one per tree.  Returns what `generate_trees` returns: one batched `Cloud` and
-    the ground-truth skeletons."""
+    the ground-truth skeletons; with `beams=True` also `scan_skeletons`' extras with every beam of the scan (`beam_dir`,
+    `beam_range`, `beam_scanner`, `origins`), the input of `occupancy.beam_tally`."""
     from ..scan import scan_skeletons, scanner_ring, skeleton_box
 
     seeds = [int(s) for s in np.atleast_1d(np.asarray(seeds, dtype=object))]
@@ -252,8 +253,8 @@ def scan_trees(seeds, scanners=3, *, step_deg=0.1, radius=6.0, height=1.5, scale
         leaves = [(c, np.full(len(c), leaf_radius, np.float32)) for c in centres]
     rings = [scanner_ring(int(scanners), radius, height, skeleton_box(sk, None if leaves is None else leaves[i]), step_deg, seed=seeds[i],
                           range_noise=range_noise) for i, sk in enumerate(skeletons)]
-    cloud, _ = scan_skeletons(skeletons, rings, leaves, form, dev)
-    return cloud, skeletons
+    cloud, extras = scan_skeletons(skeletons, rings, leaves, form, dev, beams=bool(beams))
+    return (cloud, skeletons, extras) if beams else (cloud, skeletons)
 
 
 # --------------------------------------------------------------------------------------------------------- dataset ---

@@ -173,6 +173,9 @@ def radius_at_height(xyz, radii, level, up=1) -> float:
     return float("nan")
 
 
+LEAF_AREA = "leaf_area_m2"  # the optional last column: measure_trees(..., plant_area=)
+
+
 def tree_columns(n_classes: int) -> tuple:
     return TREE_HEAD + tuple(f"points_class_{k}" for k in range(n_classes)) + TREE_TAIL
 
@@ -258,7 +261,8 @@ class TreeInventory:
     def split(self) -> list:
         """The clouds of a batch, each as its own call gives it (the class columns end at the cloud's own last class)."""
         first = len(TREE_HEAD)
-        C = len(self.tree_columns) - first - len(TREE_TAIL)
+        extra = tuple(self.tree_columns[-1:]) if tuple(self.tree_columns[-1:]) == (LEAF_AREA,) else ()
+        C = len(self.tree_columns) - first - len(TREE_TAIL) - len(extra)
         out = []
         for k in range(self.n_clouds):
             sel = self.trees[:, 0] == k
@@ -270,7 +274,7 @@ class TreeInventory:
             rows[:, 0] = 0
             orphans = self.orphans[self.orphans[:, 0] == k].copy()
             orphans[:, 0] = 0
-            out.append(TreeInventory(trees, rows, self.profile[sel], self.cell, tree_columns(keep), orphans, self.breast_height, self.up))
+            out.append(TreeInventory(trees, rows, self.profile[sel], self.cell, tree_columns(keep) + extra, orphans, self.breast_height, self.up))
         return out
 
     def save(self, directory) -> None:
@@ -333,14 +337,16 @@ def root_positions(flat: FlatSkeletons, branches) -> np.ndarray:
 
 
 def measure_trees(cloud, skeleton, segmentation=None, cell=0.1, layers=256, breast_height=1.3, up=1, max_distance=None,
-                  device=None, ground=None) -> TreeInventory:
+                  device=None, ground=None, plant_area=None) -> TreeInventory:
     """Every tree of `skeleton` measured on the points of `cloud` segmented onto it.  Takes what `segment_cloud` takes: a `Cloud` or
     [n,3] points with a `TreeSkeleton`, a `DisjointTreeSkeleton` or the flat arrays of `save_skeleton_npz`; a collated `Cloud` with a
     list of skeletons, one per cloud.  `segmentation`: the `CloudSegmentation` of these points and this skeleton when the caller has
     it (else `segment_cloud` runs here, with `max_distance`).  One tally call and one read-back for the whole batch.
     `ground`: the `terrain.GroundModel` of these clouds, in their frame.  A tree's `base` is then the terrain under the first vertex of
     its root branch (`ground.surface_at`), and `height` and the level of the DBH follow from it; where the terrain is unknown there
-    (NaN) the base stays the tree's lowest point.  None changes nothing."""
+    (NaN) the base stays the tree's lowest point.  None changes nothing.
+    `plant_area`: [n_trees] m2, one value per tree in `skeleton_owners` order -- what `occupancy.BeamTally.plant_area_by_label` gives
+    for the tree rows of the returns (`point_rows`); it becomes the last column, `leaf_area_m2`.  None adds no column."""
     from .segmentation import segment_cloud
 
     pts, seg_off, skeletons, _, n_clouds = points_and_skeletons(cloud, skeleton, device, "measure_trees")
@@ -382,7 +388,13 @@ def measure_trees(cloud, skeleton, segmentation=None, cell=0.1, layers=256, brea
             if len(sel):
                 ground_base[sel] = ground.surface_at(roots[sel].astype(np.float32), cloud=c).cpu().numpy()
     trees = tree_table(flat, branches, box, counts, area_cells, profile, float(cell), float(breast_height), int(up), ground_base)
-    return TreeInventory(trees, branches, profile, float(cell), tree_columns(counts.shape[1]), orphans, float(breast_height), int(up), n_clouds)
+    columns = tree_columns(counts.shape[1])
+    if plant_area is not None:
+        area = (plant_area.detach().cpu().numpy() if torch.is_tensor(plant_area) else np.asarray(plant_area)).astype(np.float64).reshape(-1)
+        if area.shape[0] != T:
+            raise ValueError(f"measure_trees: plant_area has {area.shape[0]} value(s) for {T} tree(s)")
+        trees, columns = np.concatenate([trees, area[:, None]], axis=1), columns + (LEAF_AREA,)
+    return TreeInventory(trees, branches, profile, float(cell), columns, orphans, float(breast_height), int(up), n_clouds)
 
 
 def summary(inv: TreeInventory) -> str:

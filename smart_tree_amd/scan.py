@@ -1,8 +1,9 @@
 """A virtual terrestrial laser scanner: skeletons ray-cast to occluded, labelled clouds (csrc/scan.hip).
 
 `python -m smart_tree_amd.scan skeleton=<skeleton.npz> out=<.npz|.ply> [scanners=3] [radius=6] [height=1.5] [step_deg=0.05]
-[range_noise=0.002] [seed=0] [form=auto] [device=cuda:0]` scans a saved skeleton from a ring of positions around it and writes the
-cloud (`util.file.load_cloud` reads it back).  Overrides are parsed by config.py, as for `segmentation` / `render`.
+[range_noise=0.002] [seed=0] [form=auto] [device=cuda:0] [beams=<beams.npz>]` scans a saved skeleton from a ring of positions around
+it and writes the cloud (`util.file.load_cloud` reads it back); with `beams=` also every beam of the scan, returned or not, as the
+file `python -m smart_tree_amd.occupancy` reads.  Overrides are parsed by config.py, as for `segmentation` / `render`.
 
 What `dataset.synthetic.generate_trees` cannot give: a cloud that sees one side of a stem from each position, thins out with the
 square of the range and has shadows wherever a nearer branch stands in the way.  The surface of a tube is the zero set of the
@@ -191,7 +192,7 @@ def grid_plan(ws, cloud: int = 0) -> dict:
             "sweep": int(rec[28:32].view(np.int32)[0])}
 
 
-def scan_skeletons(skeletons, scanners, leaves=None, form="auto", device=None):
+def scan_skeletons(skeletons, scanners, leaves=None, form="auto", device=None, beams=False):
     """Scan a batch of clouds.  `skeletons`: one per cloud, anything `FlatSkeletons` takes (a `DisjointTreeSkeleton` gives mutual
     occlusion between its trees); `scanners`: per cloud a list of `Scanner`; `leaves`: per cloud None or (centres [L,3], radii [L]),
     spheres of class 1 that shadow and are hit like the wood.  Returns a batched `Cloud` (`xyz`, zero `rgb`, `medial_vector`,
@@ -199,7 +200,10 @@ def scan_skeletons(skeletons, scanners, leaves=None, form="auto", device=None):
     beams), `scanner` (its scanner's index in cloud-major order), `range` (un-noised), `segment` (the tube, in `FlatSkeletons`'
     order per cloud with the cloud's leaves behind its tubes, counted through the batch; `tube_off` [B+1] has each cloud's first),
     `dir` (the beam's unit direction, world coordinates).  All scanners of a call rotate about the same axis (`Scanner.up`): tubes,
-    leaves and positions are permuted into that frame for the cast and the points back, which rounds nothing."""
+    leaves and positions are permuted into that frame for the cast and the points back, which rounds nothing.
+    `beams=True` adds every beam of the call, returned or not, for `occupancy.beam_tally`: `beam_dir` [R,3] (world coordinates),
+    `beam_range` [R] (un-noised, +inf without a return), `beam_scanner` [R] int32 and `origins` [S,3] (the scanners' positions, world
+    coordinates, cloud-major order)."""
     skeletons, scanners = list(skeletons), [list(s) for s in scanners]
     B = len(skeletons)
     if len(scanners) != B or (leaves is not None and len(leaves) != B):
@@ -248,6 +252,12 @@ def scan_skeletons(skeletons, scanners, leaves=None, form="auto", device=None):
                   res["class_l"].view(-1, 1), seg_off=seg_off)
     extras = {"ray": res["ray"], "scanner": scanner.to(torch.int32), "range": res["range"].index_select(0, ray), "segment": res["segment"],
               "dir": world(res["dir"].index_select(0, ray)), "tube_off": tube_off, "ray_off": res["ray_off"]}
+    if beams:
+        n_rays = torch.from_numpy(np.diff(res["ray_off"])).to(dev)
+        positions = np.asarray([s.position for per_cloud in scanners for s in per_cloud], np.float32).reshape(-1, 3)
+        extras.update(beam_dir=world(res["dir"]), beam_range=res["range"], origins=world(torch.from_numpy(positions).to(dev)),
+                      beam_scanner=torch.repeat_interleave(torch.arange(len(n_rays), dtype=torch.int32, device=dev), n_rays,
+                                                           output_size=int(res["ray_off"][-1])))
     return cloud, extras
 
 
@@ -267,9 +277,9 @@ def skeleton_box(skeleton, leaves=None):
 
 # ---------------------------------------------------------------------------------------------------------------- cli ---
 DEFAULTS = {"skeleton": None, "out": None, "scanners": 3, "radius": 6.0, "height": 1.5, "step_deg": 0.05, "range_noise": 0.002,
-            "seed": 0, "form": "auto", "device": "cuda:0"}
+            "seed": 0, "form": "auto", "device": "cuda:0", "beams": None}
 USAGE = ("usage: python -m smart_tree_amd.scan skeleton=<skeleton.npz> out=<.npz|.ply> [scanners=3] [radius=6] [height=1.5] "
-         "[step_deg=0.05] [range_noise=0.002] [seed=0] [form=auto|dense|grid] [device=]")
+         "[step_deg=0.05] [range_noise=0.002] [seed=0] [form=auto|dense|grid] [device=] [beams=<beams.npz>]")
 
 
 def main(argv=None) -> Cloud:
@@ -287,8 +297,11 @@ def main(argv=None) -> Cloud:
     skeleton = load_any_skeleton(cfg["skeleton"])
     ring = scanner_ring(int(cfg["scanners"]), float(cfg["radius"]), float(cfg["height"]), skeleton_box(skeleton), float(cfg["step_deg"]),
                         seed=int(cfg["seed"]), range_noise=float(cfg["range_noise"]))
-    cloud, extras = scan_skeletons([skeleton], [ring], form=str(cfg["form"]), device=cfg["device"])
+    cloud, extras = scan_skeletons([skeleton], [ring], form=str(cfg["form"]), device=cfg["device"], beams=cfg["beams"] is not None)
     cloud.seg_off = None
+    if cfg["beams"] is not None:
+        from .occupancy import save_beams
+        save_beams(str(cfg["beams"]), extras["origins"], extras["beam_scanner"], extras["beam_dir"], extras["beam_range"])
     out.parent.mkdir(parents=True, exist_ok=True)
     if out.suffix == ".npz":
         save_cloud(out, cloud)
